@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpix/s of lens-undistort + 5x5 filter on 4K float32 frames.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (LensDistortion-style undistort, bilinear,
 BORDER_CONSTANT, then a 5x5 Gaussian given as an explicit kernel, 'reflect'
@@ -16,11 +16,24 @@ are independent, every rank processes its own batch (weak scaling), no
 data-path collective; torch.distributed (gloo) is used only for the barrier
 and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline`
-(dominant kernel; COMPULSORY HBM bytes of the launch / HIP-event time, the
-map pair counted once per launch), `other_configs` (BASELINE configurations
-C2..C5 kernel-only, C4 also PCIe-inclusive; N=1 only) and `cpu_baseline` (the
-oracle C restatement timed on this box's host cores, N=1 only).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line
+(rank 0) with the contract fields plus `roofline` (dominant kernel;
+COMPULSORY HBM bytes of the launch / HIP-event time of the timed steps, the
+map pair counted once per launch).
+
+--full adds everything that takes runs of its own: the class probe of the
+batch buffers, the first launches one event pair each, the no-settle pass, the
+dense loop beside the separable one, the median over per-step events, the
+result of the timed launches against the oracle (a mismatch fails the run),
+the device copy, `other_configs` (BASELINE configurations C2..C5 kernel-only,
+C4 also PCIe-inclusive; N=1 only), `cpu_baseline` (the oracle C restatement
+timed on the host cores, N=1 only) and, at N > 1, the end-to-end leg.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's result
+batch) as float32 .npy files: `result_frame0.npy` (the first frame, whole) and
+`result_sample.npy` (a fixed, seeded sample of the whole batch, flat), 64 MB
+at most in all.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 """
 import argparse
 import ctypes
@@ -150,6 +163,35 @@ def timed(ctx, fn, steps, warmup):
     e1.record()
     ctx.synchronize()
     return e0.elapsed_ms(e1) / steps
+
+
+DUMP_SEED = 20240607
+DUMP_FRAME_MAX_BYTES = 40 << 20
+DUMP_SAMPLE_MAX = 4 << 20   # float32 elements: 16 MiB
+
+
+def dump_outputs(out_dir, d_dst):
+    """the result batch of the last timed step as float32 .npy files: the first frame whole (when it fits
+    40 MiB) and a seeded sample of DUMP_SAMPLE_MAX elements drawn over the whole batch (flat indices,
+    sorted; the same for every run with the same batch shape).  Frames are copied back one at a time."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = d_dst.shape[0]
+    fsize = d_dst.size // n
+    total = d_dst.size
+    if total <= DUMP_SAMPLE_MAX:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE_MAX, dtype=np.int64))
+    sample = np.empty(idx.size, np.float32)
+    host = np.empty(d_dst.shape[1:], np.float32)
+    bounds = np.searchsorted(idx, np.arange(n + 1, dtype=np.int64) * fsize)
+    for i in range(n):
+        d_dst.frame(i).get(out=host)
+        if i == 0 and host.nbytes <= DUMP_FRAME_MAX_BYTES:
+            np.save(os.path.join(out_dir, 'result_frame0.npy'), host)
+        lo, hi = bounds[i], bounds[i + 1]
+        sample[lo:hi] = host.reshape(-1)[idx[lo:hi] - i * fsize]
+    np.save(os.path.join(out_dir, 'result_sample.npy'), sample)
 
 
 def timed_settled(ctx, fn, steps, warmup, settle_s=0.2):
@@ -528,17 +570,22 @@ def main():
                     choices=['fused_map', 'fused_analytic', 'two_kernel', 'two_kernel_analytic'])
     ap.add_argument('--height', type=int, default=H4K)
     ap.add_argument('--width', type=int, default=W4K)
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the oracle check and the cpu_baseline leg')
     ap.add_argument('--placements', type=int, default=0,
                     help="candidate allocations per large block of the context pool (0 = the library's "
                          'default: IMGPROC_HIP_PLACE, 1 = every allocation as it comes; 2 = the better of two)')
     ap.add_argument('--no-settle', action='store_true',
                     help='skip the untimed clock-settling launches of the setup phase')
     ap.add_argument('--e2e-frames', type=int, default=64,
-                    help='N > 1: uint16 frames every rank streams host -> device -> host in the end-to-end leg '
+                    help='--full, N > 1: uint16 frames every rank streams host -> device -> host in the end-to-end leg '
                          '(0 skips it)')
     ap.add_argument('--no-configs', action='store_true',
-                    help='skip the other_configs leg (BASELINE configurations C2..C5)')
+                    help='--full: skip the other_configs leg (BASELINE configurations C2..C5)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: class probe, first launches, no-settle and dense-loop passes, '
+                         'median, oracle check, device copy, other_configs, cpu_baseline, end-to-end leg (N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the result of the last timed step (rank 0) as float32 .npy files into DIR')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -584,11 +631,13 @@ def main():
     # (profiles/r05_micro.txt).  The buffers above are taken as the driver
     # hands them out (the library's default since round 5; --placements 2 / IMGPROC_HIP_PLACE=2:
     # the better of two allocations, logged below).  What class this run drew is reported, not
-    # chosen: the pool's strip-shaped probe (a plain 3x3 filter from one half of the block into
-    # the other) on both buffers before the frames go in - ~0.377 ms: the fast class of a 2 GiB
+    # chosen (--full): the pool's strip-shaped probe (a plain 3x3 filter from one half of the block
+    # into the other) on both buffers before the frames go in - ~0.377 ms: the fast class of a 2 GiB
     # block, ~0.39: the middle one, ~0.425: the slow one.
-    probe_ms = {'source': round(ctx._probe_block(d_src.ptr, d_src.nbytes), 4),
-                'result': round(ctx._probe_block(d_dst.ptr, d_dst.nbytes), 4)}
+    probe_ms = None
+    if args.full:
+        probe_ms = {'source': round(ctx._probe_block(d_src.ptr, d_src.nbytes), 4),
+                    'result': round(ctx._probe_block(d_dst.ptr, d_dst.nbytes), 4)}
     d_src.set(frames)
     dmx, dmy = ops.build_undistort_map(K, dcoef, K, h, w, ctx=ctx, device=True)
     ctx.synchronize()
@@ -632,30 +681,29 @@ def main():
     # which loop the library takes for this call: the bench's 5x5 is outer(g, g) - an exact outer product goes
     # to the separable 5 + 5 loop (knob rank1_sep, on by default; csrc/fused.hip::rank1_chain)
     routed0 = ctx.get_tuning('rank1_routed')
-    # the very first launches of this process, one event pair each: the clock ramp of a GPU that idled while
-    # the host built the frames, as a driver-side record sees it (config.first_launch_ms)
+    # --full: the very first launches of this process, one event pair each: the clock ramp of a GPU that idled
+    # while the host built the frames, as a driver-side record sees it (config.first_launch_ms)
     n_first = 30
-    fev = [ctx.event() for _ in range(n_first + 1)]
-    fev[0].record()
-    for i in range(n_first):
-        step()
-        fev[i + 1].record()
-    ctx.synchronize()
-    first_ms = [round(fev[i].elapsed_ms(fev[i + 1]), 4) for i in range(n_first)]
-    del fev
-    sep_route = ctx.get_tuning('rank1_routed') > routed0
-    if sep_route:
-        kname_dense = kname
-        kname = kname.replace('wave_stencil_kernel', 'wave_sep_kernel').replace(',5>', ',5+5>')
-
-    # What a run WITHOUT any preparation sees (clocks still ramping up from idle): the first
-    # min(steps, 20) steps after the driver's warm-up count, reported as no_settle_*.
     ns_steps = min(args.steps, 20)
-    ns_ms = timed(ctx, step, ns_steps, args.warmup)
+    first_ms = ns_ms = None
+    if args.full:
+        fev = [ctx.event() for _ in range(n_first + 1)]
+        fev[0].record()
+        for i in range(n_first):
+            step()
+            fev[i + 1].record()
+        ctx.synchronize()
+        first_ms = [round(fev[i].elapsed_ms(fev[i + 1]), 4) for i in range(n_first)]
+        del fev
+
+        # What a run WITHOUT any preparation sees (clocks still ramping up from idle): the first
+        # min(steps, 20) steps after the driver's warm-up count, reported as no_settle_*.
+        ns_ms = timed(ctx, step, ns_steps, args.warmup)
 
     # Setup, not measurement: let the GPU clocks settle (reported as config.clock_settle_launches;
-    # --no-settle skips it and the no_settle_* numbers above are then the whole story).
-    settle = 0 if args.no_settle else max(20, 4800 // B)
+    # --no-settle skips it).  A plain run makes the launches that --full times above here, untimed, so
+    # that both enter the timed region with the same load behind them.
+    settle = 0 if args.no_settle else max(20, 4800 // B) + (0 if args.full else n_first + args.warmup + ns_steps)
     for _ in range(settle):
         step()
     ctx.synchronize()
@@ -676,11 +724,19 @@ def main():
     per_rank_ms = gather_over_ranks(el / args.steps * 1e3)
     el = max_over_ranks(el)
     ev_ms = e0.elapsed_ms(e1)  # HIP events on the stream the kernels ran on
+    sep_route = ctx.get_tuning('rank1_routed') > routed0
+    if sep_route:
+        kname_dense = kname
+        kname = kname.replace('wave_stencil_kernel', 'wave_sep_kernel').replace(',5>', ',5+5>')
+
+    # what the last timed step left in d_dst, before anything below launches into it again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_dst)
 
     # the dense 5x5 loop on the same buffers, same process (knob rank1_sep = 0): what the call cost before
     # round 6 routed outer products to the separable loop - reported beside the line, never as `value`
     dense_ms = None
-    if sep_route and rank == 0:
+    if args.full and sep_route and rank == 0:
         old_knob = ctx.set_tuning(rank1_sep=0)
         try:
             dense_ms = timed(ctx, step, max(20, min(args.steps, 60)), 5)
@@ -690,21 +746,23 @@ def main():
     # SURVEY section 8(d) asks for the MEDIAN of >= 20 iterations: a second, untimed-for-`value`
     # pass with one event pair per step (the contract's `value` / `ms_per_step` stay the
     # whole-region figures above)
-    n_med = max(20, min(args.steps, 100))
-    evs = [ctx.event() for _ in range(n_med + 1)]
-    evs[0].record()
-    for i in range(n_med):
-        step()
-        evs[i + 1].record()
-    ctx.synchronize()
-    per_step = sorted(evs[i].elapsed_ms(evs[i + 1]) for i in range(n_med))
-    med_ms = per_step[n_med // 2]
-    del evs
+    n_med = med_ms = None
+    if args.full:
+        n_med = max(20, min(args.steps, 100))
+        evs = [ctx.event() for _ in range(n_med + 1)]
+        evs[0].record()
+        for i in range(n_med):
+            step()
+            evs[i + 1].record()
+        ctx.synchronize()
+        per_step = sorted(evs[i].elapsed_ms(evs[i + 1]) for i in range(n_med))
+        med_ms = per_step[n_med // 2]
+        del evs
 
     # N > 1: the end-to-end half (every rank: its own uint16 frames host -> device -> host).  The kernel-only
     # line above scales trivially; this is the leg SURVEY section 8(e) names as the real limiter.
     e2e = None
-    if dist_on and args.e2e_frames > 0 and (h, w) == (H4K, W4K):
+    if args.full and dist_on and args.e2e_frames > 0 and (h, w) == (H4K, W4K):
         ms_e2e, ok_e2e, cpu_span = end_to_end_c4(ia, ops, ctx.device_id, rank, h, w, args.e2e_frames, barrier)
         failed = 0.0 if ok_e2e else 1.0
         e2e_ms = gather_over_ranks(ms_e2e)
@@ -725,7 +783,7 @@ def main():
         # the result the timed launches left in d_dst, against the oracle (first and last frame of
         # the batch; the oracle is the checker here, never the thing measured)
         checked = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             from oracle import oracle as orc
             orc.build()
             orc.set_threads(max(1, min(usable_cores(), orc.max_threads())))
@@ -743,14 +801,15 @@ def main():
                        'note': 'result of the timed launches vs oracle/oracle.c (map-based '
                                'bilinear remap + 5x5, double accumulation); relative to '
                                'max(|ref|, 1e-3 max|ref|)'}
-        # what a plain device copy of the same buffers reaches in this run (read + write): the
-        # practical ceiling of a streaming kernel on this box, next to the 8 TB/s of the guide
-        # (after the oracle check: it overwrites the result batch)
-        copy_ms = timed(ctx, lambda: d_dst.copy_from(d_src), 20, 3)
-        copy_gbs = 2.0 * d_src.nbytes / (copy_ms * 1e-3) / 1e9
+        if args.full:
+            # what a plain device copy of the same buffers reaches in this run (read + write): the
+            # practical ceiling of a streaming kernel on this box, next to the 8 TB/s of the guide
+            # (after the oracle check: it overwrites the result batch)
+            copy_ms = timed(ctx, lambda: d_dst.copy_from(d_src), 20, 3)
+            copy_gbs = 2.0 * d_src.nbytes / (copy_ms * 1e-3) / 1e9
         # for reference: the same launches on a pair of buffers taken as the driver hands them out
         # (placement off), allocated now - what a caller that bypasses the pool's choice would see
-        if args.variant.startswith('fused') and ctx._place_n > 1:
+        if args.full and args.variant.startswith('fused') and ctx._place_n > 1:
             keep_n, ctx._place_n = ctx._place_n, 1
             try:
                 s_raw = ctx.empty((B, h, w), np.float32)
@@ -779,21 +838,12 @@ def main():
                        'frames_per_step_per_gpu': B, 'variant': args.variant,
                        'path': ('separable 5 + 5 loop: the 5x5 kernel is an exact outer product (library default, '
                                 'knob rank1_sep)' if sep_route else 'dense 5x5 loop'),
-                       'probe_src_ms': probe_ms['source'], 'probe_dst_ms': probe_ms['result'],
-                       'first_launch_ms': first_ms,
                        'per_rank_ms_per_step': [round(v, 4) for v in per_rank_ms],
-                       'clock_settle_launches': settle, 'buffer_placement': placement,
-                       'no_settle_ms_per_step': round(ns_ms, 4),
-                       'no_settle_value': round(world * px / ns_ms / 1e3, 1),
-                       'no_settle_steps': ns_steps,
+                       'clock_settle_launches': settle,
                        'sharding': 'independent frames, %d rank(s), no collective' % world},
             'roofline': {'bound': 'hbm', 'achieved': round(ach, 1), 'peak': HBM_PEAK_GBS,
                          'unit': 'GB/s', 'frac': round(ach / HBM_PEAK_GBS, 4),
                          'traffic': traffic, 'traffic_source': traffic_src,
-                         'checked_vs_oracle': checked,
-                         'median_step_ms': round(med_ms, 4),
-                         'median_frac': round(compulsory / (med_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         'median_over_steps': n_med,
                          'bytes_model': 'compulsory: source + result per frame, map pair once '
                                         'per launch',
                          'compulsory_bytes_per_launch': compulsory // launches
@@ -805,28 +855,40 @@ def main():
                                     '(dense 25 taps -> separable 5 + 5: profiles/r06_micro.txt); HBM is the roofline the '
                                     'compulsory bytes are priced against, not what saturates',
                          'kernel': kname, 'launches_per_step': launches,
-                         'dense_loop': ({'kernel': kname_dense, 'ms_per_step': round(dense_ms, 4),
-                                         'frac': round(compulsory / (dense_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                         'note': 'the same call with rank1_sep = 0, same buffers, same process'}
-                                        if dense_ms else None),
                          'avg_step_ms_hip_events': round(ev_ms / args.steps, 4),
                          'literal_survey_8d': {
                              'bytes_per_px': literal_px,
                              'achieved': round(literal_px * px / step_s / 1e9, 1),
                              'frac': round(literal_px * px / step_s / 1e9 / HBM_PEAK_GBS, 4),
                              'note': 'charges the map pair to every frame; NOT the roofline '
-                                     'fraction'},
-                         'no_settle_frac': round(compulsory / (ns_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         'device_copy': {
-                             'achieved': round(copy_gbs, 1), 'unit': 'GB/s',
-                             'kernel_vs_copy': round(ach / copy_gbs, 4),
-                             'note': 'hipMemcpyAsync device-to-device of the source batch into '
-                                     'the result batch in this run, read + write bytes; context '
-                                     'for `peak`, not a substitute for it'}},
+                                     'fraction'}},
         }
+        if args.full:
+            line['config'].update({
+                'probe_src_ms': probe_ms['source'], 'probe_dst_ms': probe_ms['result'],
+                'first_launch_ms': first_ms, 'buffer_placement': placement,
+                'no_settle_ms_per_step': round(ns_ms, 4),
+                'no_settle_value': round(world * px / ns_ms / 1e3, 1),
+                'no_settle_steps': ns_steps})
+            line['roofline'].update({
+                'checked_vs_oracle': checked,
+                'median_step_ms': round(med_ms, 4),
+                'median_frac': round(compulsory / (med_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                'median_over_steps': n_med,
+                'dense_loop': ({'kernel': kname_dense, 'ms_per_step': round(dense_ms, 4),
+                                'frac': round(compulsory / (dense_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                'note': 'the same call with rank1_sep = 0, same buffers, same process'}
+                               if dense_ms else None),
+                'no_settle_frac': round(compulsory / (ns_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                'device_copy': {
+                    'achieved': round(copy_gbs, 1), 'unit': 'GB/s',
+                    'kernel_vs_copy': round(ach / copy_gbs, 4),
+                    'note': 'hipMemcpyAsync device-to-device of the source batch into '
+                            'the result batch in this run, read + write bytes; context '
+                            'for `peak`, not a substitute for it'}})
         if e2e is not None:
             line['end_to_end'] = e2e
-        if world == 1 and not args.no_configs and (h, w) == (H4K, W4K):
+        if args.full and world == 1 and not args.no_configs and (h, w) == (H4K, W4K):
             del d_src, d_dst, d_tmp
             extra = []
             if args.variant == 'fused_map' and B != 128:
@@ -883,7 +945,7 @@ def main():
                 except MemoryError:
                     pass
             line['other_configs'] = extra + other_configs(ctx, ia, ops)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line['cpu_baseline'] = cpu_baseline(h, w, K, dcoef, k5)
         # a result that is not the oracle's is not a measurement: say so in the line and fail
         bad = checked is not None and not (checked['max_rel_err'] <= checked['tolerance'])
