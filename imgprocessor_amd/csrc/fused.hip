@@ -7,14 +7,15 @@ using namespace ipa;
 void ipa_fused_sep_launch_a(ipa_ctx*, const FusedCall&, const FusedSep&);  // 3, 5 taps
 void ipa_fused_sep_launch_b(ipa_ctx*, const FusedCall&, const FusedSep&);  // 7, 9 taps
 void ipa_fused_sep_launch_c(ipa_ctx*, const FusedCall&, const FusedSep&);  // 1 tap: the remap alone
-void ipa_fused_sep_launch_c16(ipa_ctx*, const FusedCall&);                   // ... uint16 into uint16 (cv2's 16U arithmetic)
-void ipa_fused_sep_launch_c8(ipa_ctx*, const FusedCall&);                    // ... uint8 into uint8 (cv2's 8U fixed point)
+int ipa_fused_sep_launch_c16(ipa_ctx*, const FusedCall&);  // ... uint16 into uint16 (cv2's 16U arithmetic); 1 = not covered
+int ipa_fused_sep_launch_c8(ipa_ctx*, const FusedCall&);   // ... uint8 into uint8 (cv2's 8U fixed point); 1 = not covered
 
 int ipa_fused_launch_k3(ipa_ctx*, const FusedCall&);
 int ipa_fused_launch_k5(ipa_ctx*, const FusedCall&);
 int ipa_fused_launch_k7(ipa_ctx*, const FusedCall&);
 int ipa_fused_big_launch(ipa_ctx*, const FusedCall&, int K);  // fused_big.hip; 1 = not covered
 int ipa_check_interp_border(ipa_ctx* ctx, int interp, int border);  // remap.hip
+int make_undistort_coord(ipa_ctx* ctx, const double* K, const double* d, const double* newK, UndistortCoord* c);  // remap.hip
 #if IPA_WITH_TILE_CHAIN
 // tile_chain.hip: 0 = launched, 1 = not a chain for that kernel
 int ipa_tile_chain_launch(ipa_ctx* ctx, const void* d_src, int sh, int sw, long src_pitch, const double* M,
@@ -23,64 +24,92 @@ int ipa_tile_chain_launch(ipa_ctx* ctx, const void* d_src, int sh, int sw, long 
                           int interp, int border_mode, double border_value, int cby, int cbx);
 #endif
 
-static int inv3f(const double* m, double* o) {
-  double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-  double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-  double det = a * A + b * B + c * C;
-  if (det == 0 || det != det) return -1;
-  double id = 1.0 / det;
-  o[0] = A * id; o[1] = -(b * i - c * h) * id; o[2] = (b * f - c * e) * id;
-  o[3] = B * id; o[4] = (a * i - c * g) * id;  o[5] = -(a * f - c * d) * id;
-  o[6] = C * id; o[7] = -(a * h - b * g) * id; o[8] = (a * e - b * d) * id;
-  return 0;
+// Which chains are ONE kernel (float32 results); the others take two launches through the workspace (two_launch_remap).
+// dense: a taps x taps filter (taps 0: rectangular), else separable taps + taps (taps 1: the remap alone, remap.hip's strip
+// remap); coord_kind 0 maps, 1 lens model, 2 homography - the lens model of a call that goes through its cached map is 0.
+//   dense 3 / 5 / 7   float32 frames: bilinear and the two bicubics, any coordinates; uint16 frames: bilinear, maps or the
+//                     lens model; uint8 frames: bilinear, maps (fused_k*.hip; 7x7 resident or streamed, see
+//                     ipa_remap_conv2d_dev);
+//   dense 9 / 11      map-based bilinear remaps of float32 frames (fused_big.hip, knobs big_fused / stream_k): for the
+//                     rest the sampling source plus 9 / 11 running rows exceed the VGPR budget that pays;
+//   separable         bilinear, 3 / 5 / 7 / 9 taps (bicubic: built and correct, but 16 taps per sample on the K - 1 extra
+//                     halo rows of every strip make it slower than two launches - 4K, 9 taps: 813 vs 694 us); integer
+//                     frames (knob sep_u16) also one tap: uint16 with maps or a homography, uint8 with maps.
+// Round 6: every other combination the standalone entry points accept - Lanczos4 / nearest taps, uint8 frames, uint16
+// frames with a homography or bicubic taps, rectangular or larger kernels - runs as two launches (it returned
+// IPA_ERR_UNSUPPORTED before): a caller of the chain gets what remap + filter give, in whatever number of launches.
+static bool chain_one_kernel(const ipa_ctx* ctx, bool dense, int src_dtype, int dst_dtype, int coord_kind, int interp,
+                             int taps) {
+  const ipa_tuning& t = ctx->tune;
+  const int base = interp & 0xff;
+  const bool linear = base == IPA_INTER_LINEAR;
+  if (dst_dtype != IPA_F32) return false;
+  if (dense) {
+    if (taps == 9 || taps == 11)
+      return t.big_fused && taps >= t.stream_k && src_dtype == IPA_F32 && coord_kind == 0 && linear;
+    if (!(taps == 3 || taps == 5 || taps == 7)) return false;
+    if (src_dtype == IPA_F32) return linear || base == IPA_INTER_CUBIC_CV || base == IPA_INTER_CUBIC_KEYS;
+    if (src_dtype == IPA_U16) return linear && coord_kind != 2;
+    return src_dtype == IPA_U8 && linear && coord_kind == 0;
+  }
+  if (!linear || !(taps == 3 || taps == 5 || taps == 7 || taps == 9 || (taps == 1 && src_dtype != IPA_F32))) return false;
+  if (src_dtype == IPA_F32) return true;
+  if (src_dtype == IPA_U16) return t.sep_u16 && coord_kind != 1;
+  return src_dtype == IPA_U8 && t.sep_u16 && coord_kind == 0;
+}
+int ipa_chain_one_kernel(const ipa_ctx* ctx, int src_dtype, int dst_dtype, int coord_kind, int interp) {  // (remap.hip)
+  return chain_one_kernel(ctx, false, src_dtype, dst_dtype, coord_kind, interp, 1);
 }
 
 // Dense K x K kernels that are an outer product ky (x) kx - the bench's 5x5 is outer(g, g), and the reference itself
 // obtains its Gaussians separably (scipy.ndimage.gaussian_filter: filters/standardDeviation.py:23,
-// filters/fastFilter.py:42) - run on the separable K + K chain when that chain is ONE kernel for the call
-// (fused_sep_common's one_kernel: float32 frames, bilinear taps, 3 / 5 / 7 / 9 taps).  64 x 4K maps + 5x5: K + K
-// = 10 instead of K * K = 25 multiply-adds per pixel on the same strips.  Knob rank1_sep bit 0; the two loops
-// differ by the order of a float32 sum only (both within 1e-5 of the oracle's double sum).
-static bool rank1_chain(ipa_ctx* ctx, const double* kernel, int kh, int kw, int src_dtype, int dst_dtype,
-                        int interp, double* ky, double* kx, bool maps = false, bool u8_maps = false) {
-  if (!(ctx->tune.rank1_sep & 1) || !kernel || kh != kw) return false;
-  if (!(kh == 3 || kh == 5 || kh == 7 || kh == 9)) return false;
-  // (uint16 frames: where the separable chain is one kernel for them - maps, homographies; knob sep_u16)
-  const bool src_ok = src_dtype == IPA_F32 || ((src_dtype == IPA_U16 || (src_dtype == IPA_U8 && u8_maps)) && maps && ctx->tune.sep_u16 != 0);
-  if (!src_ok || dst_dtype != IPA_F32 || (interp & 0xff) != IPA_INTER_LINEAR) return false;
+// filters/fastFilter.py:42) - run on the separable K + K chain when that chain is ONE kernel for the call.  64 x 4K maps
+// + 5x5: K + K = 10 instead of K * K = 25 multiply-adds per pixel on the same strips.  Knob rank1_sep bit 0; the two
+// loops differ by the order of a float32 sum only (both within 1e-5 of the oracle's double sum).
+static bool rank1_chain(ipa_ctx* ctx, const double* kernel, int kh, int kw, int src_dtype, int dst_dtype, int coord_kind,
+                        int interp, double* ky, double* kx) {
+  if (!(ctx->tune.rank1_sep & 1) || !kernel || kh != kw || kh == 1) return false;
+  if (!chain_one_kernel(ctx, false, src_dtype, dst_dtype, coord_kind, interp, kh)) return false;
   return ipa_rank1_factor(kernel, kh, kw, ky, kx);
 }
 
-// K = 9, 11: map-based bilinear remaps of float32 frames run in one kernel (fused_big.hip);
-// for the rest (bicubic, analytic coordinates, uint16 frames) the sampling source plus 9 / 11
-// running rows exceed the VGPR budget that pays: the chain runs as two launches through the
-// context workspace: remap kernel -> 9x9 / 11x11 filter.
-// Round 6: so does every combination the standalone entry points accept and no fused kernel is
-// built for - Lanczos4 / nearest taps, uint8 frames, uint16 frames with a homography or bicubic
-// taps, rectangular or larger kernels (they returned IPA_ERR_UNSUPPORTED before): a caller of the
-// chain gets what remap + filter give, in whatever number of launches.
-static bool dense_chain_built(int src_dtype, int coord_kind, int interp, int kh, int kw) {
-  const int base = interp & 0xff;
-  if (kh != kw || !(kh == 3 || kh == 5 || kh == 7)) return false;
-  if (src_dtype == IPA_F32)
-    return base == IPA_INTER_LINEAR || base == IPA_INTER_CUBIC_CV || base == IPA_INTER_CUBIC_KEYS;
-  if (src_dtype == IPA_U16) return base == IPA_INTER_LINEAR && coord_kind != 2;
-  if (src_dtype == IPA_U8) return base == IPA_INTER_LINEAR && coord_kind == 0;   // (8-bit camera frames, maps)
-  return false;
+// where a chain's coordinates come from, as its caller gave them
+struct ChainCoords {
+  int kind;                       // 0 maps, 1 lens model, 2 homography
+  const float *mx, *my;           // 0
+  long map_pitch;
+  const double *K, *dist5, *newK; // 1
+  const double* M;                // 2
+};
+static int chain_coord(ipa_ctx* ctx, const ChainCoords& c, FusedCall& f) {
+  f.coord_kind = c.kind;
+  if (c.kind == 0) f.map = MapCoord{c.mx, c.my, c.map_pitch};
+  else if (c.kind == 1) return make_undistort_coord(ctx, c.K, c.dist5, c.newK, &f.und);
+  else for (int i = 0; i < 9; i++) f.hom.m[i] = c.M[i];
+  return IPA_OK;
 }
-static int big_kernel_tmp(ipa_ctx* ctx, int src_dtype, int coord_kind, int interp, int kh, int kw, int dst_dtype,
-                          int dh, int dw, int n_frames, void** tmp) {
-  const bool big = kh == kw && (kh == 9 || kh == 11);
-  if (!big) {
-    if (dense_chain_built(src_dtype, coord_kind, interp, kh, kw)) return 1;   // one kernel
-    // (anything the two launches would reject themselves goes on to the fused path's own checks)
-    if (dst_dtype != IPA_F32 || dh <= 0 || dw <= 0 || n_frames < 1 || kh < 1 || kw < 1) return 1;
-  }
-  IPA_REQUIRE(ctx, dst_dtype == IPA_F32, "fused remap+filter writes float32");
+
+// the first of the two launches of a chain that is not one kernel: the remap into the context workspace (float32 frames
+// of dh x dw, back to back); the filter follows from there.  Same results: the fused kernels round the remapped rows to
+// float32 as well.
+static int two_launch_remap(ipa_ctx* ctx, const ChainCoords& c, const void* d_src, int src_dtype, int sh, int sw,
+                            long src_pitch, int dh, int dw, int n_frames, long src_frame_stride, int interp,
+                            int border_mode, double border_value) {
+  IPA_REQUIRE(ctx, dh > 0 && dw > 0 && n_frames >= 1, "empty image");
   int rc = ipa_ws_reserve(ctx, (size_t)n_frames * dh * dw * 4);
   if (rc) return rc;
-  *tmp = ctx->ws;
-  return IPA_OK;
+  const long fs = (long)dh * dw;
+  switch (c.kind) {
+    case 0:
+      return ipa_remap_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, c.mx, c.my, c.map_pitch, ctx->ws, IPA_F32, dh, dw,
+                           dw, n_frames, src_frame_stride, fs, interp, border_mode, border_value);
+    case 1:
+      return ipa_undistort_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, c.K, c.dist5, c.newK, ctx->ws, IPA_F32, dh, dw,
+                               dw, n_frames, src_frame_stride, fs, interp, border_mode, border_value);
+    default:
+      return ipa_warp_perspective_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, c.M, ctx->ws, IPA_F32, dh, dw, dw,
+                                      n_frames, src_frame_stride, fs, interp, border_mode, border_value);
+  }
 }
 
 // validation + everything of a FusedCall that does not depend on the filter
@@ -127,18 +156,32 @@ static int fused_fill(ipa_ctx* ctx, FusedCall& f, const void* d_src, int src_dty
   return IPA_OK;
 }
 
-static int fused_common(ipa_ctx* ctx, FusedCall& f, const void* d_src, int src_dtype, int sh,
+// remap -> K x K filter: one kernel where chain_one_kernel says so (prefer_two: rotated warps, below), else two launches
+// - the remap into the workspace, then the plain filter.  (Calls the two launches would reject themselves go on to the
+// fused path's own checks.)
+static int fused_common(ipa_ctx* ctx, const ChainCoords& c, const void* d_src, int src_dtype, int sh,
                         int sw, long src_pitch, const double* kernel, int kh, int kw, void* d_dst,
                         int dst_dtype, int dh, int dw, long dst_pitch, int n_frames,
                         long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
-                        double border_value, int cbx, int cby) {
+                        double border_value, int cbx, int cby, bool prefer_two = false) {
+  const bool one = chain_one_kernel(ctx, true, src_dtype, dst_dtype, c.kind, interp, kh == kw ? kh : 0);
+  if (one ? prefer_two : dst_dtype == IPA_F32 && dh > 0 && dw > 0 && n_frames >= 1 && kh >= 1 && kw >= 1) {
+    int rc = two_launch_remap(ctx, c, d_src, src_dtype, sh, sw, src_pitch, dh, dw, n_frames, src_frame_stride, interp,
+                              border_mode, border_value);
+    if (rc) return rc;
+    return ipa_conv2d_dev(ctx, ctx->ws, IPA_F32, dh, dw, dw, kernel, kh, kw, nullptr, 0, d_dst, dst_pitch, n_frames,
+                          (long)dh * dw, dst_frame_stride, cbx, cby, 0.0);
+  }
   IPA_REQUIRE(ctx, kernel, "null pointer");
   if (kh != kw || !(kh == 3 || kh == 5 || kh == 7 || kh == 9 || kh == 11))
     IPA_UNSUPPORTED(ctx, "fused remap+filter is built for square 3/5/7/9/11 kernels (got %dx%d); "
                          "use ipa_remap_dev + ipa_conv2d_dev", kh, kw);
-  int rc = fused_fill(ctx, f, d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw,
-                      dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp, border_mode,
-                      border_value, cbx, cby);
+  FusedCall f;
+  int rc = chain_coord(ctx, c, f);
+  if (rc) return rc;
+  rc = fused_fill(ctx, f, d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw,
+                  dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp, border_mode,
+                  border_value, cbx, cby);
   if (rc) return rc;
   f.kernel = kernel;
   IPA_HIP(ctx, hipSetDevice(ctx->device));
@@ -153,41 +196,29 @@ static int fused_common(ipa_ctx* ctx, FusedCall& f, const void* d_src, int src_d
   return IPA_OK;
 }
 
-// remap -> separable filter.  One kernel where wave_sep_kernel covers the case; otherwise
-// `two(tmp)` materialises the remap in the context workspace and the plain separable filter
-// follows (same results: the fused kernel rounds the remapped row to float32 as well).
-template <typename TwoLaunch>
-static int fused_sep_common(ipa_ctx* ctx, FusedCall& f, TwoLaunch two, const void* d_src,
+// remap -> separable filter: one kernel (wave_sep_kernel) where chain_one_kernel says so, else two launches as above
+static int fused_sep_common(ipa_ctx* ctx, const ChainCoords& c, const void* d_src,
                             int src_dtype, int sh, int sw, long src_pitch, const double* ky, int nky,
                             const double* kx, int nkx, void* d_dst, int dst_dtype, int dh, int dw,
                             long dst_pitch, int n_frames, long src_frame_stride,
                             long dst_frame_stride, int interp, int border_mode, double border_value,
                             int cby, int cbx, bool prefer_two = false) {
+  FusedCall f;
+  int rc = chain_coord(ctx, c, f);
+  if (rc) return rc;
   IPA_REQUIRE(ctx, ky && kx && nky > 0 && nkx > 0 && (nky & 1) && (nkx & 1),
               "ky / kx must be given with odd lengths");
   IPA_REQUIRE(ctx, dst_dtype == IPA_F32, "remap + separable filter writes float32");
-  const int base = interp & 0xff;
-  // bicubic: built and correct, but 16 taps per sample on the K-1 extra halo rows of every
-  // strip make it slower than two launches (4K, 9 taps: 813 vs 694 us) -> two launches
-  // (uint16 frames: with maps or a homography - f.coord_kind is set by the caller before it comes here)
-  // (one tap - the remap alone - is built for uint16 frames: remap.hip::strip_remap_takes)
-  // (uint8 frames: with maps only)
-  const bool u8_maps = src_dtype == IPA_U8 && f.coord_kind == 0 && ctx->tune.sep_u16 != 0;
-  const bool one_kernel = nky == nkx && (nky == 3 || nky == 5 || nky == 7 || nky == 9 || (nky == 1 && src_dtype != IPA_F32)) &&
-                          (src_dtype == IPA_F32 || u8_maps || (src_dtype == IPA_U16 && f.coord_kind != 1 && ctx->tune.sep_u16 != 0)) &&
-                          base == IPA_INTER_LINEAR && !prefer_two;
-  if (!one_kernel) {
-    IPA_REQUIRE(ctx, dh > 0 && dw > 0 && n_frames >= 1, "empty image");
-    int rc = ipa_ws_reserve(ctx, (size_t)n_frames * dh * dw * 4);
-    if (rc) return rc;
-    rc = two(ctx->ws);
+  if (prefer_two || !chain_one_kernel(ctx, false, src_dtype, dst_dtype, c.kind, interp, nky == nkx ? nky : 0)) {
+    rc = two_launch_remap(ctx, c, d_src, src_dtype, sh, sw, src_pitch, dh, dw, n_frames, src_frame_stride, interp,
+                          border_mode, border_value);
     if (rc) return rc;
     return ipa_sepconv2d_dev(ctx, ctx->ws, IPA_F32, dh, dw, dw, ky, nky, kx, nkx, d_dst, dst_pitch,
                              n_frames, (long)dh * dw, dst_frame_stride, cby, cbx, 0.0);
   }
-  int rc = fused_fill(ctx, f, d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw,
-                      dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp, border_mode,
-                      border_value, cbx, cby);
+  rc = fused_fill(ctx, f, d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw,
+                  dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp, border_mode,
+                  border_value, cbx, cby);
   if (rc) return rc;
   FusedSep q{ky, kx, nky, 0.0f};
   IPA_HIP(ctx, hipSetDevice(ctx->device));
@@ -235,20 +266,17 @@ int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int 
                         const float* d_mapy, long map_pitch, void* d_dst, int dh, int dw, long dst_pitch, int n_frames,
                         long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
                         double border_value) {
-  const ipa_tuning& t = ctx->tune;
-  if (!t.strip_remap || !t.sep_u16 || !t.frames_wg || !t.frames_inner || !t.pipe) return 1;
+  if (!ctx->tune.strip_remap || !ctx->tune.sep_u16) return 1;
   // uint16: cv2's arithmetic is what 'linear_cv_q5' names ('linear' = exact coordinates in double: the gather kernel);
   // uint8: every bilinear remap is cv2's fixed point
   if (dtype == IPA_U16 ? interp != (IPA_INTER_LINEAR | IPA_INTER_Q5)
                        : (dtype != IPA_U8 || (interp & 0xff) != IPA_INTER_LINEAR || (interp & ~(0xff | IPA_INTER_Q5)) != 0))
     return 1;
-  // (counts that are no multiple of 4: from 7 frames on as a head of whole workgroups + the LAST four frames again -
-  //  as the chains do, fused_impl.hpp::fused_split_tail; 5 and 6 frames stay with the gather kernel)
-  if (n_frames < 4 || (n_frames % 4 != 0 && n_frames < 7) || n_frames > 65535) return 1;
+  // (the frame count and the grid: the shared-loop plan in fused_sep_c.hip)
+  if (n_frames < 1 || n_frames > 65535) return 1;
   if (!d_src || !d_dst || !d_mapx || !d_mapy || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || (dw & 3) != 0) return 1;
   if (src_pitch < sw || dst_pitch < dw || map_pitch < dw || src_pitch >= (1l << 23)) return 1;
   if (((size_t)(sh - 1) * src_pitch + sw) * ipa_dtype_size(dtype) >= (1ull << 31)) return 1;
-  if ((unsigned long)(((dw + 255) / 256) * ((dh + 15) / 16)) * (unsigned long)n_frames >= (1ul << 31)) return 1;
   FusedCall f;
   f.coord_kind = 0;
   f.map = MapCoord{d_mapx, d_mapy, map_pitch};
@@ -261,21 +289,8 @@ int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int 
   const double r = rint(border_value), top = dtype == IPA_U16 ? 65535.0 : 255.0;
   f.cval = r > 0 ? (r < top ? r : top) : 0;
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  auto launch = [&](const FusedCall& g) {
-    if (dtype == IPA_U16) ipa_fused_sep_launch_c16(ctx, g);
-    else ipa_fused_sep_launch_c8(ctx, g);
-  };
-  if (n_frames % 4 == 0) {
-    launch(f);
-  } else {
-    FusedCall head = f, tail = f;
-    head.n_frames = n_frames - n_frames % 4;
-    tail.n_frames = 4;
-    tail.src = f.src + (long)(n_frames - 4) * f.src_frame_bytes;
-    tail.p.dst = f.p.dst + (long)(n_frames - 4) * f.p.dst_frame_elems * (long)ipa_dtype_size(dtype);
-    launch(head);
-    launch(tail);
-  }
+  rc = dtype == IPA_U16 ? ipa_fused_sep_launch_c16(ctx, f) : ipa_fused_sep_launch_c8(ctx, f);
+  if (rc) return rc;
   IPA_HIP(ctx, hipGetLastError());
   ctx->strip_remaps++;
   return IPA_OK;
@@ -292,15 +307,8 @@ int ipa_remap_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int 
                             int conv_border_x) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, d_mapx && d_mapy && map_pitch >= dw, "bad map arguments");
-  FusedCall f;
-  f.coord_kind = 0;
-  f.map = MapCoord{d_mapx, d_mapy, map_pitch};
-  auto two = [&](void* tmp) {
-    return ipa_remap_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, tmp,
-                         IPA_F32, dh, dw, dw, n_frames, src_frame_stride, (long)dh * dw, interp,
-                         border_mode, border_value);
-  };
-  return fused_sep_common(ctx, f, two, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
+  const ChainCoords c{0, d_mapx, d_mapy, map_pitch};
+  return fused_sep_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
                           dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                           dst_frame_stride, interp, border_mode, border_value, conv_border_y,
                           conv_border_x);
@@ -324,19 +332,8 @@ int ipa_undistort_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, 
                                    src_frame_stride, dst_frame_stride, interp, border_mode,
                                    border_value, conv_border_y, conv_border_x);
   }
-  FusedCall f;
-  f.coord_kind = 1;
-  UndistortCoord& c = f.und;
-  IPA_REQUIRE(ctx, inv3f(newK, c.ir) == 0, "newK is singular");
-  c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
-  c.k1 = dist5[0]; c.k2 = dist5[1]; c.p1 = dist5[2]; c.p2 = dist5[3]; c.k3 = dist5[4];
-  c.affine = (c.ir[6] == 0.0 && c.ir[7] == 0.0 && c.ir[8] == 1.0) ? 1 : 0;
-  auto two = [&](void* tmp) {
-    return ipa_undistort_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, tmp, IPA_F32,
-                             dh, dw, dw, n_frames, src_frame_stride, (long)dh * dw, interp,
-                             border_mode, border_value);
-  };
-  return fused_sep_common(ctx, f, two, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
+  const ChainCoords c{1, nullptr, nullptr, 0, K, dist5, newK};
+  return fused_sep_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
                           dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                           dst_frame_stride, interp, border_mode, border_value, conv_border_y,
                           conv_border_x);
@@ -351,14 +348,7 @@ int ipa_warp_perspective_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_
                                        int conv_border_x) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, M, "null matrix");
-  FusedCall f;
-  f.coord_kind = 2;
-  for (int i = 0; i < 9; i++) f.hom.m[i] = M[i];
-  auto two = [&](void* tmp) {
-    return ipa_warp_perspective_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, tmp, IPA_F32, dh,
-                                    dw, dw, n_frames, src_frame_stride, (long)dh * dw, interp,
-                                    border_mode, border_value);
-  };
+  const ChainCoords c{2, nullptr, nullptr, 0, nullptr, nullptr, nullptr, M};
   const bool rotated = dh > 0 && dw > 0 &&
                        rotated_warp_in_two_launches(ctx, M, src_dtype, dst_dtype, interp, dh, dw, n_frames);
 #if IPA_WITH_TILE_CHAIN   // experiment builds only (tools/tile_chain): the one-launch chain, slower than the two launches
@@ -404,7 +394,7 @@ int ipa_warp_perspective_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_
     }
   }
 #endif
-  return fused_sep_common(ctx, f, two, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
+  return fused_sep_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, ky, nky, kx, nkx, d_dst,
                           dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                           dst_frame_stride, interp, border_mode, border_value, conv_border_y,
                           conv_border_x, rotated);
@@ -420,7 +410,7 @@ int ipa_remap_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh,
   IPA_REQUIRE(ctx, d_mapx && d_mapy && map_pitch >= dw, "bad map arguments");
   {
     double ky[9], kx[9];
-    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, interp, ky, kx, true, true)) {
+    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, 0, interp, ky, kx)) {
       ctx->rank1_routed++;
       return ipa_remap_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, ky, kh,
                                      kx, kw, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -428,8 +418,9 @@ int ipa_remap_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh,
                                      conv_border_x);
     }
   }
+  const ChainCoords c{0, d_mapx, d_mapy, map_pitch};
   // 9x9 / 11x11 on float32 frames: one kernel (fused_big.hip); big_fused = 0 is the tuning
-  // knob that sends them through the two launches below instead
+  // knob that sends them through the two launches instead
   const bool big_fused = ctx->tune.big_fused != 0;
   // 7x7 as well: with the sampling source's scalar state, 49 resident coefficients overflow
   // the SGPR file (331 spills); streamed, the 4K chain measured 489 -> 449 us (float32) and
@@ -441,17 +432,15 @@ int ipa_remap_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh,
   // coefficients resident as op_sel pairs on the hand-scheduled loop: C4 64 x 4K 1.475 -> 1.333 ms
   // (knob pipe7 = 0: streamed).  float32 frames measure the same either way (1.484 / 1.484: two
   // more tap registers per footprint, 141 VGPRs) and stay on the streamed kernel.
-  const bool shared7 = kh == 7 && kw == 7 && ctx->tune.pipe7 != 0 && ctx->tune.frames_wg != 0 &&
-                       ctx->tune.frames_inner != 0 && (interp & 0xff) == IPA_INTER_LINEAR &&
-                       n_frames % 4 == 0 && dst_dtype == IPA_F32 &&
-                       src_dtype == IPA_U16;
+  const bool shared7 = kh == 7 && kw == 7 && ctx->tune.pipe7 != 0 && (interp & 0xff) == IPA_INTER_LINEAR &&
+                       dst_dtype == IPA_F32 && src_dtype == IPA_U16 &&
+                       shared_loop_plan(ctx, true, n_frames, true) == kSharedLoop;
   const bool streamed = kh >= stream_k && kh >= 7 && kh <= 11 && !shared7;
   if (big_fused && kh == kw && streamed &&
       (src_dtype == IPA_F32 || (kh == 7 && src_dtype == IPA_U16)) && dst_dtype == IPA_F32 &&
       kernel) {
     FusedCall f;
-    f.coord_kind = 0;
-    f.map = MapCoord{d_mapx, d_mapy, map_pitch};
+    chain_coord(ctx, c, f);
     int rc = fused_fill(ctx, f, d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw,
                         dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp,
                         border_mode, border_value, conv_border_x, conv_border_y);
@@ -465,22 +454,7 @@ int ipa_remap_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh,
       return IPA_OK;
     }
   }
-  void* tmp = nullptr;
-  int big = big_kernel_tmp(ctx, src_dtype, 0, interp, kh, kw, dst_dtype, dh, dw, n_frames, &tmp);
-  if (big < 0) return big;
-  if (big == 0) {
-    int rc = ipa_remap_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, tmp,
-                           IPA_F32, dh, dw, dw, n_frames, src_frame_stride, (long)dh * dw, interp,
-                           border_mode, border_value);
-    if (rc) return rc;
-    return ipa_conv2d_dev(ctx, tmp, IPA_F32, dh, dw, dw, kernel, kh, kw, nullptr, 0, d_dst,
-                          dst_pitch, n_frames, (long)dh * dw, dst_frame_stride, conv_border_x,
-                          conv_border_y, 0.0);
-  }
-  FusedCall f;
-  f.coord_kind = 0;
-  f.map = MapCoord{d_mapx, d_mapy, map_pitch};
-  return fused_common(ctx, f, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
+  return fused_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
                       dh, dw, dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp,
                       border_mode, border_value, conv_border_x, conv_border_y);
 }
@@ -496,7 +470,7 @@ int ipa_undistort_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
   IPA_REQUIRE(ctx, K && dist5 && newK, "K, dist5 and newK must be given");
   {
     double ky[9], kx[9];
-    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, interp, ky, kx, ctx->tune.lens_cache != 0, ctx->tune.lens_cache != 0)) {
+    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, ctx->tune.lens_cache ? 0 : 1, interp, ky, kx)) {
       ctx->rank1_routed++;
       return ipa_undistort_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, ky, kh, kx, kw,
                                          d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -516,26 +490,8 @@ int ipa_undistort_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
                                 dst_frame_stride, interp, border_mode, border_value, conv_border_x,
                                 conv_border_y);
   }
-  void* tmp = nullptr;
-  int big = big_kernel_tmp(ctx, src_dtype, 1, interp, kh, kw, dst_dtype, dh, dw, n_frames, &tmp);
-  if (big < 0) return big;
-  if (big == 0) {
-    int rc = ipa_undistort_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, tmp,
-                               IPA_F32, dh, dw, dw, n_frames, src_frame_stride, (long)dh * dw,
-                               interp, border_mode, border_value);
-    if (rc) return rc;
-    return ipa_conv2d_dev(ctx, tmp, IPA_F32, dh, dw, dw, kernel, kh, kw, nullptr, 0, d_dst,
-                          dst_pitch, n_frames, (long)dh * dw, dst_frame_stride, conv_border_x,
-                          conv_border_y, 0.0);
-  }
-  FusedCall f;
-  f.coord_kind = 1;
-  UndistortCoord& c = f.und;
-  IPA_REQUIRE(ctx, inv3f(newK, c.ir) == 0, "newK is singular");
-  c.fx = K[0]; c.fy = K[4]; c.cx = K[2]; c.cy = K[5];
-  c.k1 = dist5[0]; c.k2 = dist5[1]; c.p1 = dist5[2]; c.p2 = dist5[3]; c.k3 = dist5[4];
-  c.affine = (c.ir[6] == 0.0 && c.ir[7] == 0.0 && c.ir[8] == 1.0) ? 1 : 0;
-  return fused_common(ctx, f, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
+  const ChainCoords c{1, nullptr, nullptr, 0, K, dist5, newK};
+  return fused_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
                       dh, dw, dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp,
                       border_mode, border_value, conv_border_x, conv_border_y);
 }
@@ -550,7 +506,7 @@ int ipa_warp_perspective_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dty
   IPA_REQUIRE(ctx, M, "null matrix");
   {
     double ky[9], kx[9];
-    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, interp, ky, kx, true)) {
+    if (rank1_chain(ctx, kernel, kh, kw, src_dtype, dst_dtype, 2, interp, ky, kx)) {
       ctx->rank1_routed++;
       return ipa_warp_perspective_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, ky, kh, kx, kw, d_dst,
                                                 dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -558,31 +514,12 @@ int ipa_warp_perspective_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dty
                                                 conv_border_y, conv_border_x);
     }
   }
-  void* tmp = nullptr;
-  int big = big_kernel_tmp(ctx, src_dtype, 2, interp, kh, kw, dst_dtype, dh, dw, n_frames, &tmp);
-  if (big < 0) return big;
-  if (big != 0 && kernel && dh > 0 && dw > 0 &&
-      rotated_warp_in_two_launches(ctx, M, src_dtype, dst_dtype, interp, dh, dw, n_frames)) {
-    int rc = ipa_ws_reserve(ctx, (size_t)n_frames * dh * dw * 4);
-    if (rc) return rc;
-    tmp = ctx->ws;
-    big = 0;
-  }
-  if (big == 0) {
-    int rc = ipa_warp_perspective_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, tmp, IPA_F32, dh,
-                                      dw, dw, n_frames, src_frame_stride, (long)dh * dw, interp,
-                                      border_mode, border_value);
-    if (rc) return rc;
-    return ipa_conv2d_dev(ctx, tmp, IPA_F32, dh, dw, dw, kernel, kh, kw, nullptr, 0, d_dst,
-                          dst_pitch, n_frames, (long)dh * dw, dst_frame_stride, conv_border_x,
-                          conv_border_y, 0.0);
-  }
-  FusedCall f;
-  f.coord_kind = 2;
-  for (int i = 0; i < 9; i++) f.hom.m[i] = M[i];
-  return fused_common(ctx, f, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
+  const ChainCoords c{2, nullptr, nullptr, 0, nullptr, nullptr, nullptr, M};
+  const bool rotated = kernel && dh > 0 && dw > 0 &&
+                       rotated_warp_in_two_launches(ctx, M, src_dtype, dst_dtype, interp, dh, dw, n_frames);
+  return fused_common(ctx, c, d_src, src_dtype, sh, sw, src_pitch, kernel, kh, kw, d_dst, dst_dtype,
                       dh, dw, dst_pitch, n_frames, src_frame_stride, dst_frame_stride, interp,
-                      border_mode, border_value, conv_border_x, conv_border_y);
+                      border_mode, border_value, conv_border_x, conv_border_y, rotated);
 }
 
 }  // extern "C"

@@ -39,51 +39,36 @@ struct FusedCall {
   const double* kernel;
 };
 
-// Batches whose frame count is no multiple of the workgroup's IPA_WPB frames cannot share
-// footprint records in every workgroup and used to fall back to the per-frame loop as a whole
-// (15 x 4K frames: 0.398 ms against 0.268 for 16).  They run as TWO launches of the shared loop
-// instead: the first n - n % IPA_WPB frames, then the LAST IPA_WPB frames - up to three of those a
-// second time, with the same bits.  (Not when source and result may overlap: the second launch
-// would then read what the first wrote.)
-// which strip-height table a fused launch takes (wave_strip_height's `piped`): the tall strips of
-// the shared-record loop only where that loop runs - the frames of a workgroup are frames of one
-// strip (knobs frames_wg / frames_inner, n a multiple of IPA_WPB); the per-frame loop, whose rim
-// strips are on the chunked path, keeps the short ones (64 x 4K with frames_wg = 0: 1.53 ms on
-// 144-row strips)
-template <typename Src, int K> static int fused_strip_piped(const ipa_ctx* ctx, int n_frames) {
-  const bool shared_run = shared_capable<Src, K>::value && IPA_PIPE && IPA_PIPE_SHARED &&
-                          ctx->tune.frames_wg != 0 && ctx->tune.frames_inner != 0 &&
-                          n_frames % IPA_WPB == 0;
-  return shared_run ? 2 : 0;
-}
-
-template <typename Src, int K> static bool fused_split_tail(const ipa_ctx* ctx, const FusedCall& f) {
-  if (!(shared_capable<Src, K>::value && IPA_PIPE && IPA_PIPE_SHARED)) return false;
-  if (!ctx->tune.frames_wg || !ctx->tune.frames_inner) return false;
-  // (from 7 frames on: 5 and 6 frames measure faster on the per-frame loop - 0.124 against 0.158 ms)
-  if (f.n_frames < 2 * IPA_WPB - 1 || f.n_frames % IPA_WPB == 0) return false;
+// The shared-loop plan of a fused call (wave_stencil.hpp::shared_loop_plan, with its source and result byte ranges) and,
+// when it is split, the two launches: part[0] the first n - n % IPA_WPB frames, part[1] the last IPA_WPB frames.
+static inline SharedPlan fused_plan(const ipa_ctx* ctx, bool capable, const FusedCall& f, FusedCall (&part)[2]) {
+  const long ds = (long)ipa_dtype_size(f.dst_dt);
   const char* s0 = f.src;
   const char* s1 = f.src + (long)f.n_frames * f.src_frame_bytes;
   const char* d0 = f.p.dst;
-  const char* d1 = f.p.dst + (long)f.n_frames * f.p.dst_frame_elems * 4;
-  return s1 <= d0 || d1 <= s0;
+  const char* d1 = f.p.dst + (long)f.n_frames * f.p.dst_frame_elems * ds;
+  const SharedPlan plan = shared_loop_plan(ctx, capable, f.n_frames, s1 <= d0 || d1 <= s0);
+  if (plan == kSharedSplit) {
+    part[0] = part[1] = f;
+    part[0].n_frames = f.n_frames - f.n_frames % IPA_WPB;
+    part[1].n_frames = IPA_WPB;
+    part[1].src += (long)(f.n_frames - IPA_WPB) * f.src_frame_bytes;
+    part[1].p.dst += (long)(f.n_frames - IPA_WPB) * f.p.dst_frame_elems * ds;
+  }
+  return plan;
 }
 
-// batches on the shared-record loop whose coordinates come from the homography: its double
-// coordinates (two fused-multiply-add chains and a division per pixel) are evaluated ONCE per
-// (matrix, geometry) into the plan buffer (stored_coords.hpp) and the record producers read them
-// as a table - the C3 chain spent a third of its time evaluating them once per four frames
-static inline bool fused_wants_stored_coords(const ipa_ctx* ctx, const FusedCall& f) {
-  const int smin = ctx->tune.stored_coords;
-  return smin > 0 && f.n_frames >= smin && ctx->tune.pipe != 0 && ctx->tune.frames_wg != 0 &&
-         ctx->tune.frames_inner != 0 && (f.n_frames % IPA_WPB == 0 || f.n_frames >= 2 * IPA_WPB - 1);
-}
-
+// Homography batches on the shared-record loop (knob stored_coords: from that many frames): its double coordinates (two
+// fused-multiply-add chains and a division per pixel) are evaluated ONCE per (matrix, geometry) into the plan buffer
+// (stored_coords.hpp) and the record producers read them as a table - the C3 chain spent a third of its time evaluating
+// them once per four frames.
 template <typename ST, int INTERP, typename Coord, int K>
 static void fused_launch_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c) {
   using Src = SampleRowSrc<ST, INTERP, Coord>;
+  FusedCall part[2];
+  const SharedPlan plan = fused_plan(ctx, shared_capable<Src, K>::value, f, part);
   if constexpr (std::is_same<Coord, HomographyCoord>::value && shared_capable<Src, K>::value) {
-    if (fused_wants_stored_coords(ctx, f)) {
+    if (ctx->tune.stored_coords > 0 && f.n_frames >= ctx->tune.stored_coords && plan != kPerFrameLoop) {
       StoredCoord<double> sc;
       if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0) {
         fused_launch_one<ST, INTERP, StoredCoord<double>, K>(ctx, f, sc);
@@ -91,14 +76,9 @@ static void fused_launch_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c) {
       }
     }
   }
-  if (fused_split_tail<Src, K>(ctx, f)) {
-    FusedCall head = f, tail = f;
-    head.n_frames = f.n_frames - f.n_frames % IPA_WPB;
-    tail.n_frames = IPA_WPB;
-    tail.src = f.src + (long)(f.n_frames - IPA_WPB) * f.src_frame_bytes;
-    tail.p.dst = f.p.dst + (long)(f.n_frames - IPA_WPB) * f.p.dst_frame_elems * 4;
-    fused_launch_one<ST, INTERP, Coord, K>(ctx, head, c);
-    fused_launch_one<ST, INTERP, Coord, K>(ctx, tail, c);
+  if (plan == kSharedSplit) {
+    fused_launch_one<ST, INTERP, Coord, K>(ctx, part[0], c);
+    fused_launch_one<ST, INTERP, Coord, K>(ctx, part[1], c);
     return;
   }
   Weights<float, K * K> w;
@@ -112,8 +92,9 @@ static void fused_launch_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c) {
   WaveParams p = f.p;
   using G = wave_geom<K, geom_halo<Src, K, false>::value>;
   p.strips_x = (p.dw + G::OW - 1) / G::OW;
-  p.strip_h = wave_strip_height(ctx, p.dh, p.dw, f.n_frames, K, false,
-                                fused_strip_piped<Src, K>(ctx, f.n_frames), p.strips_x);
+  // the tall strips of the shared-record loop only where that loop runs; the per-frame loop, whose rim strips are on the
+  // chunked path, keeps the short ones (64 x 4K with frames_wg = 0: 1.53 ms on 144-row strips)
+  p.strip_h = wave_strip_height(ctx, p.dh, p.dw, f.n_frames, K, false, plan == kSharedLoop ? 2 : 0, p.strips_x);
   p.strips = (unsigned)p.strips_x * (unsigned)((p.dh + p.strip_h - 1) / p.strip_h);
   // frames of one strip block run together: map-based remaps share their map rows between
   // frames (L2 fetch traffic -62 % on 16 x 4K), and even without shared rows the order measured

@@ -6,19 +6,34 @@ void ipa_fused_sep_launch_c(ipa_ctx* ctx, const ipa::FusedCall& f, const ipa::Fu
   ipa::fused_sep_k<1>(ctx, f, q);
 }
 
-// integer frames into their own type with cv2's arithmetic (wave_pipe.hpp CV16: 16U float weights / 8U fixed point): maps,
-// every strip on the shared-record loop (fused.hip::ipa_strip_remap_int launches it only then)
-template <typename T> static void strip_remap_int_launch(ipa_ctx* ctx, const ipa::FusedCall& f) {
+// integer frames into their own type with cv2's arithmetic (wave_pipe.hpp CV16: 16U float weights / 8U fixed point): maps.
+// The kernel writes such results on the shared-record loop alone, rim strips included: returns 1 - nothing launched - unless
+// the plan and wave_grid put every strip of every launch (the whole batch, or its head and tail) on that loop.
+template <typename T> static int strip_remap_int_launch(ipa_ctx* ctx, const ipa::FusedCall& f) {
   using namespace ipa;
   using Src = SampleRowSrc<T, kLinear, MapCoord>;
+  FusedCall part[2];
+  const SharedPlan plan = fused_plan(ctx, sep_shared<Src, 1>::value && IPA_PIPE_EDGE, f, part);
+  if (plan == kPerFrameLoop) return 1;
+  if (plan == kSharedLoop) part[0] = f;
+  const int parts = plan == kSharedSplit ? 2 : 1;
+  for (int i = 0; i < parts; i++) {
+    WaveParams p = part[i].p;
+    sep_grid<Src, 1>(ctx, p, part[i].n_frames);
+    if (!p.frames_wg) return 1;
+  }
   Src s;
   s.coord = f.map;
-  s.src = f.src; s.src_frame_bytes = f.src_frame_bytes; s.src_bytes = f.src_bytes;
+  s.src_frame_bytes = f.src_frame_bytes; s.src_bytes = f.src_bytes;
   s.sh = f.sh; s.sw = f.sw; s.spitch = f.spitch;
   s.border = f.border; s.q5 = 1; s.cubic_a = f.cubic_a; s.lanczos = nullptr;
   s.cval = (float)f.cval; s.ccval = 0.f; s.map_vec = f.map_vec;
   const double one = 1.0;
-  launch_sep<Src, 1, T>(ctx, f.p, s, &one, &one, f.n_frames, 0.f);
+  for (int i = 0; i < parts; i++) {
+    s.src = part[i].src;
+    launch_sep<Src, 1, T>(ctx, part[i].p, s, &one, &one, part[i].n_frames, 0.f);
+  }
+  return 0;
 }
-void ipa_fused_sep_launch_c16(ipa_ctx* ctx, const ipa::FusedCall& f) { strip_remap_int_launch<uint16_t>(ctx, f); }
-void ipa_fused_sep_launch_c8(ipa_ctx* ctx, const ipa::FusedCall& f) { strip_remap_int_launch<uint8_t>(ctx, f); }
+int ipa_fused_sep_launch_c16(ipa_ctx* ctx, const ipa::FusedCall& f) { return strip_remap_int_launch<uint16_t>(ctx, f); }
+int ipa_fused_sep_launch_c8(ipa_ctx* ctx, const ipa::FusedCall& f) { return strip_remap_int_launch<uint8_t>(ctx, f); }

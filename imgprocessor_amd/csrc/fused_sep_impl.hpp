@@ -23,8 +23,10 @@ struct FusedSep {
 template <typename ST, int INTERP, typename Coord, int K>
 static void fused_sep_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c, const FusedSep& q) {
   using Src = SampleRowSrc<ST, INTERP, Coord>;
+  FusedCall part[2];   // (the plan and the stored coordinates as in fused_impl.hpp::fused_launch_one)
+  const SharedPlan plan = fused_plan(ctx, sep_shared<Src, K>::value, f, part);
   if constexpr (std::is_same<Coord, HomographyCoord>::value && sep_shared<Src, K>::value) {
-    if (fused_wants_stored_coords(ctx, f)) {   // (see fused_impl.hpp)
+    if (ctx->tune.stored_coords > 0 && f.n_frames >= ctx->tune.stored_coords && plan != kPerFrameLoop) {
       StoredCoord<double> sc;
       if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0) {
         fused_sep_one<ST, INTERP, StoredCoord<double>, K>(ctx, f, sc, q);
@@ -32,14 +34,9 @@ static void fused_sep_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c, cons
       }
     }
   }
-  if (sep_shared<Src, K>::value && fused_split_tail<Src, 5>(ctx, f)) {   // (see fused_impl.hpp)
-    FusedCall head = f, tail = f;
-    head.n_frames = f.n_frames - f.n_frames % IPA_WPB;
-    tail.n_frames = IPA_WPB;
-    tail.src = f.src + (long)(f.n_frames - IPA_WPB) * f.src_frame_bytes;
-    tail.p.dst = f.p.dst + (long)(f.n_frames - IPA_WPB) * f.p.dst_frame_elems * 4;
-    fused_sep_one<ST, INTERP, Coord, K>(ctx, head, c, q);
-    fused_sep_one<ST, INTERP, Coord, K>(ctx, tail, c, q);
+  if (plan == kSharedSplit) {
+    fused_sep_one<ST, INTERP, Coord, K>(ctx, part[0], c, q);
+    fused_sep_one<ST, INTERP, Coord, K>(ctx, part[1], c, q);
     return;
   }
   Src s;

@@ -8,6 +8,7 @@
 int ipa_remap_launch_map(ipa_ctx*, const RemapCall&, const MapCoord&, int map_vec);
 int ipa_remap_launch_undistort(ipa_ctx*, const RemapCall&, const UndistortCoord&);
 int ipa_remap_launch_homography(ipa_ctx*, const RemapCall&, const HomographyCoord&);
+int ipa_chain_one_kernel(const ipa_ctx* ctx, int src_dtype, int dst_dtype, int coord_kind, int interp);  // fused.hip: the remap alone as one kernel
 
 // ---------------------------------------------------------------- host side --
 static int inv3(const double* m, double* o) {
@@ -22,8 +23,8 @@ static int inv3(const double* m, double* o) {
   return 0;
 }
 
-static int make_undistort_coord(ipa_ctx* ctx, const double* K, const double* d, const double* newK,
-                                UndistortCoord* c) {
+// (fused.hip builds the coordinates of its chains here too)
+int make_undistort_coord(ipa_ctx* ctx, const double* K, const double* d, const double* newK, UndistortCoord* c) {
   IPA_REQUIRE(ctx, K && d && newK, "K, dist5 and newK must be given");
   IPA_REQUIRE(ctx, inv3(newK, c->ir) == 0, "newK is singular");
   c->fx = K[0]; c->fy = K[4]; c->cx = K[2]; c->cy = K[5];
@@ -329,18 +330,18 @@ int ipa_build_undistort_map(ipa_ctx* ctx, const double* K, const double* dist5,
 // the marching strips of the fused chains with NO filter (wave_sep_kernel, K = 1: 256-px strips, no halo, both
 // passes the identity; fused_sep_c.hip): the gather kernels these calls took stream 64 x 4K in 1.28 ms, the strips in
 // 0.90 (maps; -30 %), lens model 1.42 -> 0.89, homography 1.16 -> 1.07; identical bits (tools/strip_remap_probe.py).
-// Batches of a multiple of 4 frames (the shared-footprint loop; from 7 frames on any count: whole workgroups + the last
-// four frames again) for maps and homographies that do not turn the picture; the lens model by value at any count (its
-// map is evaluated once and cached).  uint8 frames (8-bit cameras) the same with maps: 1.28 -> 0.93 ms.  float32 frames
-// stay where they are: the tile kernel is level with the strips on maps and 15 - 19 % faster on homographies.
-// (The knob sep_u16 is required too: with it off the chain entry would come back here through its two-launch form.)
+// Batches the shared-loop plan puts on the shared-footprint loop (wave_stencil.hpp::shared_loop_plan: a multiple of 4
+// frames, from 7 frames on any count) for maps and homographies that do not turn the picture; the lens model by value at
+// any count (`any_count`: its map is evaluated once and cached).  uint8 frames (8-bit cameras) the same with maps:
+// 1.28 -> 0.93 ms.  float32 frames stay where they are: the tile kernel is level with the strips on maps and 15 - 19 %
+// faster on homographies.  (fused.hip::chain_one_kernel, knob sep_u16: the chain's two-launch form would come back here)
 static bool strip_remap_takes(const ipa_ctx* ctx, const void* d_src, const void* d_dst, int src_dtype, int dst_dtype,
                               int sh, int sw, long src_pitch, int dh, int dw, long dst_pitch, int n_frames,
-                              int interp, bool maps = false) {   // (maps: uint8 frames are built with the map pair only)
-  const ipa_tuning& t = ctx->tune;
-  if (!t.strip_remap || !t.sep_u16 || !t.frames_wg || !t.frames_inner || !t.pipe) return false;
-  if ((src_dtype != IPA_U16 && !(src_dtype == IPA_U8 && maps)) || dst_dtype != IPA_F32 || !d_src || !d_dst) return false;
-  if ((interp & 0xff) != IPA_INTER_LINEAR || (interp & ~(0xff | IPA_INTER_Q5)) != 0) return false;
+                              int interp, int coord_kind, bool any_count) {
+  if (!ctx->tune.strip_remap) return false;
+  if (shared_loop_plan(ctx, true, any_count ? IPA_WPB : n_frames, true) == kPerFrameLoop) return false;
+  if (!ipa_chain_one_kernel(ctx, src_dtype, dst_dtype, coord_kind, interp) || !d_src || !d_dst) return false;
+  if ((interp & ~(0xff | IPA_INTER_Q5)) != 0) return false;
   // (what the chain kernels' 32-bit offsets hold; anything else stays with the gather kernels and their checks)
   if (sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || src_pitch < sw || dst_pitch < dw || src_pitch >= (1l << 23)) return false;
   if (((size_t)(sh - 1) * src_pitch + sw) * ipa_dtype_size(src_dtype) >= (1ull << 31) || n_frames < 1 || n_frames > 65535) return false;
@@ -380,9 +381,7 @@ int ipa_remap_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, int sw
                                  border_value);
     if (rc <= 0) return rc;
   }
-  // (a multiple of 4 frames, or from 7 on: the chain then runs whole workgroups + the last four frames again)
-  if ((n_frames % 4 == 0 || n_frames >= 7) && strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch,
-                                                                dh, dw, dst_pitch, n_frames, interp, true)) {
+  if (strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp, 0, false)) {
     ctx->strip_remaps++;
     return ipa_remap_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, &kOneTap, 1,
                                    &kOneTap, 1, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -406,8 +405,8 @@ int ipa_undistort_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, in
   UndistortCoord c;
   int rc = make_undistort_coord(ctx, K, dist5, newK, &c);
   if (rc) return rc;
-  if (ctx->tune.lens_cache && strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw,
-                                                dst_pitch, n_frames, interp)) {   // (see ipa_remap_dev)
+  if (ctx->tune.lens_cache && src_dtype == IPA_U16 &&   // (through the cached map; uint8 frames: ipa_remap_dev below)
+      strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp, 0, true)) {
     ctx->strip_remaps++;
     return ipa_undistort_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, &kOneTap, 1, &kOneTap,
                                        1, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -436,8 +435,8 @@ int ipa_warp_perspective_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
                              double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, M, "null matrix");
-  if ((n_frames % 4 == 0 || n_frames >= 7) && strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch,
-                                                                dh, dw, dst_pitch, n_frames, interp) &&
+  if (strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp,
+                        2, false) &&
       warp_row_drift(M, dh, dw) < 0.2) {   // (see ipa_remap_dev; pictures that turn stay with the gather kernels)
     ctx->strip_remaps++;
     return ipa_warp_perspective_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, &kOneTap, 1, &kOneTap, 1,

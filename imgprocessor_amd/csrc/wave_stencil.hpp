@@ -268,6 +268,23 @@ static inline dim3 wave_grid(ipa_ctx* ctx, WaveParams& p, int n_frames, int wave
   return dim3(blocks, (unsigned)n_frames);
 }
 
+// How a batch runs on a kernel with the shared-record loop (wave_run_strip_shared: the waves of a workgroup are IPA_WPB
+// frames of one strip that share their footprint records through LDS).  `capable`: the kernel's own trait
+// (shared_capable / sep_shared, plus IPA_PIPE_EDGE where the rim strips must take the loop too).
+//   kSharedLoop   the whole batch (n a multiple of IPA_WPB; wave_grid still falls back on grids past 2^31 blocks);
+//   kSharedSplit  two launches of the loop: the first n - n % IPA_WPB frames, then the LAST IPA_WPB frames - up to
+//                 three of those a second time, with the same bits (15 x 4K: 0.398 ms on the per-frame loop, 0.268 for
+//                 16).  From 7 frames on (5 and 6 measure faster per frame: 0.124 against 0.158 ms), and only where
+//                 source and result are `apart`: the second launch would otherwise read what the first wrote;
+//   kPerFrameLoop the rest.
+enum SharedPlan { kPerFrameLoop, kSharedLoop, kSharedSplit };
+static inline SharedPlan shared_loop_plan(const ipa_ctx* ctx, bool capable, int n_frames, bool apart) {
+  const ipa_tuning& t = ctx->tune;
+  if (!(capable && IPA_PIPE && IPA_PIPE_SHARED && t.pipe && t.frames_wg && t.frames_inner)) return kPerFrameLoop;
+  if (n_frames % IPA_WPB == 0) return kSharedLoop;
+  return n_frames >= 2 * IPA_WPB - 1 && apart ? kSharedSplit : kPerFrameLoop;
+}
+
 // rows [y0, y0 + nrows) of strip row syi; false: an empty strip (the clipped end of a segment)
 __device__ __forceinline__ bool wave_strip_rows(const WaveParams& p, int syi, int& y0, int& nrows) {
   if (!p.seg_count) {

@@ -340,3 +340,30 @@ def test_full_size_camera_batch_every_frame(ia, oracle, dtype):
     for f in range(n):
         want = oracle.remap(src[f], mx, my, oracle.LINEAR | oracle.Q5, oracle.CONSTANT, 7.0)
         assert np.array_equal(got[f], want), (np.dtype(dtype).name, f, int(np.abs(got[f].astype(np.int64) - want).max()))
+
+
+@pytest.mark.parametrize('dtype', [np.uint16, np.uint8])
+def test_ragged_integer_batch_whose_result_overlaps_its_source(ia, dtype):
+    """7 frames run on the strips as a head of 4 frames + the last 4 again: not when the result overlaps the source (the
+    second launch would read frames the first one wrote) - such a call takes the gather kernel.  The control: the same
+    call on separate buffers takes the strips."""
+    from imgprocessor_amd import ops
+    from imgprocessor_amd.device import dtype_id
+    ctx = ia.default_context(0)
+    n, h, w = 7, 64, 256
+    frame = h * w * np.dtype(dtype).itemsize          # a multiple of 16 bytes
+    mx, my, _, _ = radial_maps(h, w)
+    dmx, dmy = ctx.to_device(mx), ctx.to_device(my)
+
+    def remap(src_ptr, dst_ptr):
+        before = taken(ctx)
+        ctx._check(ctx._lib.ipa_remap_dev(
+            ctx.handle, src_ptr, dtype_id(dtype), h, w, w, dmx.ptr, dmy.ptr, w, dst_ptr, dtype_id(dtype), h, w, w, n,
+            h * w, h * w, ops.interp_id('linear_cv_q5'), ops.border_id('constant'), C.c_double(0.0)), 'remap')
+        ctx.synchronize()
+        return taken(ctx) - before
+
+    src, dst = ctx.to_device(frames(n, h, w, dtype)), ctx.to_device(np.zeros((n, h, w), dtype))
+    assert remap(src.ptr, dst.ptr) == 1, 'separate buffers take the strips'
+    buf = ctx.to_device(frames(n + 2, h, w, dtype))   # source: frames 0 .. 6, result: frames 2 .. 8 of one allocation
+    assert remap(buf.ptr, C.c_void_p(buf.ptr.value + 2 * frame)) == 0, 'overlapping ranges take the gather kernel'
