@@ -105,6 +105,9 @@ PROTOTYPES = {
     'ipa_resize': [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i],
     'ipa_fast_filter_stat_dev': [_vp, _vp, _i, _i, _i, _l, _i, _i, _i, _vp],
     'ipa_fast_filter_stat': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    'ipa_ste_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _i, _dp, _d, _vp, _vp, _vp, _l, _vp, _vp, _vp,
+                    _l],
+    'ipa_remove_single_pixels_dev': [_vp, _vp, _i, _i, _l, _vp, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

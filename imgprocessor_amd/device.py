@@ -324,6 +324,19 @@ class DeviceArray(object):
         self.ptr = ctx._alloc(self.nbytes)
         self._owner = True
 
+    @classmethod
+    def counts(cls, ctx, shape):
+        """int32 per-pixel counts: the state of ops.ste_update.  No kernel takes int32 images, so
+        the constructor refuses that dtype; this is the one way to allocate it."""
+        a = cls.__new__(cls)
+        a.ctx = ctx
+        a.shape = tuple(int(s) for s in shape)
+        a.dtype = np.dtype(np.int32)
+        a.nbytes = int(np.prod(a.shape, dtype=np.int64)) * 4
+        a.ptr = ctx._alloc(a.nbytes)
+        a._owner = True
+        return a
+
     @property
     def ndim(self):
         return len(self.shape)

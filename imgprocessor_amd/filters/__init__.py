@@ -9,3 +9,4 @@ from .nan_maximum_filter import nan_maximum_filter  # noqa: F401
 from .medianThreshold import medianThreshold  # noqa: F401
 from .fastFilter import fastFilter  # noqa: F401
 from .fastMean import fastMean  # noqa: F401
+from .removeSinglePixels import removeSinglePixels  # noqa: F401

@@ -558,6 +558,86 @@ def calib_prefilter(img, bg=None, ff=None, threshold=0.1, out=None, ctx=None):
     return d_out if dev else d_out.get()
 
 
+# ------------------------------------------------- single-time effects --
+STE_DTYPES = (np.uint8, np.uint16, np.float32, np.float64)
+
+
+def _ste_state(a, shape, dtype, name):
+    if not _is_dev(a) or tuple(a.shape) != shape or a.dtype != dtype:
+        raise ValueError('%s must be a %s DeviceArray of shape %s' % (name, np.dtype(dtype), shape))
+    return a
+
+
+def ste_update(frames, avg, count, thr, first_pair=False, nlf=None, nstd=4, mask=None,
+               mask_ste=None, mask_clean=None, ctx=None):
+    """single-time-effect removal over a stack (features/SingleTimeEffectDetection.py:23-75):
+    steps the running mean through `frames` and leaves the state in place.
+
+    frames: (n, h, w) or (h, w), host or DeviceArray, uint8 / uint16 / float32 / float64 (other
+    host types go to float64).  avg (float64), count (int32) and thr (float64) are (h, w)
+    DeviceArrays: the state, updated in place.  first_pair: start from frames 0 and 1 (avg =
+    min, count = 1, thr = nlf(avg) * nstd, then max(f0, f1), f2, ...); otherwise continue from the
+    state.  nlf: (minY, ax, ay) of NoiseLevelFunction.boundedFunction, evaluated on the device,
+    or None: thr already holds the threshold.  mask: the caller's clean mask for every frame
+    (host bool or device uint8).  mask_ste (OR-accumulated) and mask_clean (the last frame's)
+    are (h, w) uint8 DeviceArrays or None.  Up to 8 frames per launch (ipa_ste_dev)."""
+    ctx = _ctx_of(frames, avg, count, thr, mask, mask_ste, mask_clean, ctx=ctx)
+    if _is_dev(frames):
+        d = frames
+        if d.dtype not in STE_DTYPES:
+            raise TypeError('ste_update: device frames must be uint8/uint16/float32/float64')
+    else:
+        f = np.asarray(frames)
+        if f.dtype not in STE_DTYPES:
+            f = f.astype(np.float64)
+        d = ctx.to_device(np.ascontiguousarray(f))
+    n, h, w = as_frames(d)
+    shape = (h, w)
+    _ste_state(avg, shape, np.float64, 'avg')
+    _ste_state(count, shape, np.int32, 'count')
+    _ste_state(thr, shape, np.float64, 'thr')
+    for a, name in ((mask_ste, 'mask_ste'), (mask_clean, 'mask_clean')):
+        if a is not None:
+            _ste_state(a, shape, np.uint8, name)
+    if mask is not None:
+        if _is_dev(mask):
+            _ste_state(mask, shape, np.uint8, 'mask')
+        else:
+            m = np.broadcast_to(np.asarray(mask, dtype=bool), shape)
+            mask = ctx.to_device(np.ascontiguousarray(m, dtype=np.uint8))
+    cnlf = None
+    if nlf is not None:
+        cnlf = L.dbl(nlf, 3)
+    ctx._check(ctx._lib.ipa_ste_dev(
+        ctx.handle, d.ptr, dtype_id(d.dtype), n, h, w, w, h * w, 1 if first_pair else 0,
+        cnlf, float(nstd), avg.ptr, count.ptr, thr.ptr, w,
+        mask.ptr if mask is not None else None,
+        mask_ste.ptr if mask_ste is not None else None,
+        mask_clean.ptr if mask_clean is not None else None, w), 'ste_update')
+
+
+def remove_single_pixels(arr, out=None, ctx=None):
+    """filters/removeSinglePixels.py:4-30, not in place: a set pixel stays set only when one of
+    its <= 8 in-image neighbours is set.  Host input (any dtype, non-zero = set) gives a bool
+    array, a (h, w) uint8 DeviceArray gives a uint8 DeviceArray."""
+    dev = _is_dev(arr)
+    ctx = _ctx_of(arr, out, ctx=ctx)
+    if dev:
+        if arr.dtype != np.uint8 or arr.ndim != 2:
+            raise TypeError('remove_single_pixels needs a 2-D uint8 DeviceArray')
+        d = arr
+    else:
+        a = np.asarray(arr)
+        if a.ndim != 2:
+            raise TypeError('remove_single_pixels needs a 2-D array')
+        d = ctx.to_device(np.ascontiguousarray(a != 0, dtype=np.uint8))
+    h, w = d.shape
+    d_out = _dev_out(ctx, out, (h, w), np.uint8) if dev else DeviceArray(ctx, (h, w), np.uint8)
+    ctx._check(ctx._lib.ipa_remove_single_pixels_dev(ctx.handle, d.ptr, h, w, w, d_out.ptr, w),
+               'remove_single_pixels')
+    return d_out if dev else d_out.get().astype(bool)
+
+
 # ------------------------------------------------- fused remap -> filter --
 def _fused_out(ctx, src, out, dh, dw, n):
     odt = np.float64 if src.dtype == np.float64 else np.float32

@@ -100,6 +100,7 @@ int ipa_ctx_synchronize(ipa_ctx* ctx);
  *   "tail_rows" (chunked batches on the shared-record loop end every XCD's share of the launch on short strips -
  *   the workgroups that run while the launch drains: -1 = the measured rule by taps and launch size, 0 = uniform
  *   strips, n = short strips of n rows; same bits).
+ *   "ste_frames" (frames per launch of ipa_ste_dev: 8, the halo tile, default; 1, one launch per frame; same bits).
  *   ipa_ctx_get_tuning also answers the read-only names "tail_rows_used" (height of the short strips of the last such
  *   launch, 0 = uniform), "rank1_routed" (dense calls sent to the separable loops so far) and "group_chunk_used" (frame
  *   groups per chunk of the last launch on the shared-record loop; "group_chunk" values that do not divide
@@ -474,6 +475,38 @@ int ipa_fast_filter_stat_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, 
                              int ksize, int every, int fn, double* d_out);
 int ipa_fast_filter_stat(ipa_ctx* ctx, const void* arr, int dtype, int h, int w, int ksize,
                          int every, int fn, double* out);
+
+/* ---------------------------------------------------------------- single-time effects */
+/* replaces features/SingleTimeEffectDetection.py:23-75 (__init__ + addImage) for a given noise
+ * level function, with filters/removeSinglePixels.py:4-30 as the neighbour rule.  Per pixel
+ * (float64 throughout, every operation correctly rounded):
+ *   first_pair:  avg = min(f0, f1), count = 1                  (:39, NaN propagates)
+ *                thr = nlf(avg) * nstd                          (:44) with nlf = {minY, ax, ay}:
+ *                max(nan_to_num(ay * sqrt(avg - ax)), minY)     (camera/NoiseLevelFunction.py:94-107),
+ *                written to d_thr; nlf NULL: d_thr is an input (a threshold the caller evaluated)
+ *                the frames stepped through are then max(f0, f1), f2, ... f(n-1)   (:46-49)
+ *   otherwise:   avg / count / thr are read from the state, the frames are f0 ... f(n-1)
+ *   per frame g (addImage, :55-75):
+ *                s = g - avg > thr;  s &= one of the <= 8 in-image neighbours has s  (:62-63)
+ *                where !s && mask: count += 1, avg += (g - avg) / count              (:65-70)
+ *                mask_ste |= s (d_mask_ste, OR-accumulated)                          (:72-73)
+ *   d_mask_clean: !s of the LAST frame (:65); d_mask: the caller's clean mask (uint8, non-zero =
+ *   clean) applied to every frame of the call (:67-68), NULL = all clean.
+ * The state (d_avg float64, d_count int32, d_thr float64; state_pitch) stays in HBM between
+ * calls, so that a later call continues the stack.  d_avg, d_count and d_thr are ALWAYS required
+ * (NULL: IPA_ERR_BAD_ARG), d_thr included when an NLF is given: it is the state a continuation
+ * call reads.  nlf is a HOST pointer and is read only with first_pair.  frames: uint8 / uint16 / float32 / float64,
+ * `frame_stride` elements apart.  State, masks and frames must not overlap (IPA_ERR_BAD_ARG), and
+ * n >= 2 with first_pair.  Up to 8 frames per launch (tuning knob ste_frames = 1: one launch per
+ * frame); a call of more launches uses the context workspace. */
+int ipa_ste_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int w, long pitch,
+                long frame_stride, int first_pair, const double* nlf, double nstd, double* d_avg,
+                int* d_count, double* d_thr, long state_pitch, const unsigned char* d_mask,
+                unsigned char* d_mask_ste, unsigned char* d_mask_clean, long mask_pitch);
+/* replaces filters/removeSinglePixels.py:4-30: out = in && one of the <= 8 in-image neighbours
+ * of the pixel is set (uint8, non-zero = set).  Not in place. */
+int ipa_remove_single_pixels_dev(ipa_ctx* ctx, const unsigned char* d_in, int h, int w, long pitch,
+                                 unsigned char* d_out, long out_pitch);
 
 #ifdef __cplusplus
 }
