@@ -108,6 +108,8 @@ PROTOTYPES = {
     'ipa_ste_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _i, _dp, _d, _vp, _vp, _vp, _l, _vp, _vp, _vp,
                     _l],
     'ipa_remove_single_pixels_dev': [_vp, _vp, _i, _i, _l, _vp, _l],
+    'ipa_nl_means_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _i, _i, _d, _d, _vp, _l, _l],
+    'ipa_nan_to_zero_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

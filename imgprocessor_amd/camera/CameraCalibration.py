@@ -23,7 +23,8 @@ Kept as written in the reference:
     the reference load here and vice versa (lens entries are coefficient dicts).
 
 Not on the GPU path (NotImplementedError, no CPU fallback): single-time-effect
-removal for image stacks (:388-408), ``deblur`` (:439-444), ``denoise`` (:456).
+removal for image stacks (:388-408) and ``deblur`` (:439-444).  ``denoise`` (:456-474)
+runs on the device (ops.nl_means).
 The reference always promotes the frame to float64 (:408-410); ``dtype=`` lets
 a caller keep float32 frames (half the HBM traffic) — an extension.
 """
@@ -247,12 +248,21 @@ class CameraCalibration(object):
     # ----------------------------------------------------------------- correct --
     def correct(self, images, bgImages=None, exposure_time=None, light_spectrum=None,
                 threshold=0.1, keep_size=True, date=None, deblur=False, denoise=False,
-                dtype=np.float64):
+                dtype=np.float64, denoise_h=0.1):
+        """denoise=True: after the lens stage NaN becomes 0 and the frame goes through non-local
+        means with patch_size 7 and patch_distance 11 (:461-474), on the device.  denoise_h is
+        the cut-off `h` of the weights in the frame's own units.  The reference always runs with
+        skimage's default h = 0.1, under which a frame in camera counts comes back unchanged:
+        every patch distance is beyond the cut-off and only the pixel itself keeps a weight.  Pass
+        a denoise_h of the order of the noise level to denoise such a frame.  deblur=True is not
+        part of the HIP path."""
         print('CORRECT CAMERA ...')
         if isinstance(date, str) or date is None:
             date = {k: date for k in ('dark current', 'flat field', 'lens', 'noise', 'psf')}
-        if deblur or denoise:
-            raise NotImplementedError('deblur / denoise are not part of the HIP path')
+        if deblur:
+            raise NotImplementedError('deblur is not part of the HIP path')
+        if denoise:
+            ops._nlm_args(7, 11, denoise_h, 0.0)
         if light_spectrum is None:
             try:
                 light_spectrum = self.coeffs['light spectra'][0]
@@ -335,5 +345,9 @@ class CameraCalibration(object):
         if lens:
             print('... correct lens distortion')
             d_img = lens.correct(d_img, keepSize=keep_size)
+        # 7. denoise
+        if denoise:
+            print('... denoise ... this might take some time')
+            d_img = ops.nl_means(ops.nan_to_zero(d_img), 7, 11, h=denoise_h)
         print('DONE')
         return d_img if dev_in else d_img.get()

@@ -10,3 +10,4 @@ from .medianThreshold import medianThreshold  # noqa: F401
 from .fastFilter import fastFilter  # noqa: F401
 from .fastMean import fastMean  # noqa: F401
 from .removeSinglePixels import removeSinglePixels  # noqa: F401
+from .denoiseNLMeans import denoiseNLMeans  # noqa: F401

@@ -638,6 +638,61 @@ def remove_single_pixels(arr, out=None, ctx=None):
     return d_out if dev else d_out.get().astype(bool)
 
 
+# ------------------------------------------------------------ denoising --
+def _nlm_args(patch_size, patch_distance, h, sigma):
+    patch_size, patch_distance = int(patch_size), int(patch_distance)
+    h, sigma = float(h), float(sigma)
+    if not 2 <= patch_size <= 11:
+        raise ValueError('nl_means: patch_size must be in 2 ... 11 (got %d)' % patch_size)
+    if patch_distance < 0:
+        raise ValueError('nl_means: patch_distance must not be negative (got %d)' % patch_distance)
+    if not h > 0 or not sigma >= 0:
+        raise ValueError('nl_means: h must be positive and sigma not negative')
+    return patch_size, patch_distance, h, sigma
+
+
+def nl_means(img, patch_size=7, patch_distance=11, h=0.1, sigma=0.0, out=None, ctx=None):
+    """non-local-means denoising, skimage.restoration.denoise_nl_means(img, patch_size,
+    patch_distance, h, fast_mode=True, sigma=sigma) of scikit-image 0.18 with the exact
+    exponential (ipa_nl_means_dev; camera/CameraCalibration.py:461-474).
+
+    img: (h, w) or (n, h, w) batch of independent frames, host or DeviceArray, float32 (computed
+    in float32) or float64 (in double); integer images raise TypeError.  An even patch_size is
+    the next odd one.  patch_size <= 11; patch_distance as far as the LDS tile holds it (30 / 20
+    for float32 / float64 at patch_size 7).  Not in place: `out` (device input only) must not be
+    the source.  Returns a new array, a DeviceArray for device input."""
+    patch_size, patch_distance, h, sigma = _nlm_args(patch_size, patch_distance, h, sigma)
+    dev = _is_dev(img)
+    if not dev:
+        img = np.asarray(img)
+    if np.dtype(img.dtype) not in (np.float32, np.float64):
+        raise TypeError('nl_means needs float32 / float64 frames (got %s)' % np.dtype(img.dtype))
+    if len(img.shape) not in (2, 3) or min(img.shape[-2:]) < 2 or img.shape[0] < 1:
+        raise ValueError('nl_means takes a (h, w) image or (n, h, w) batch with h, w >= 2, got shape %s'
+                         % (tuple(img.shape),))
+    if out is not None and (not dev or out is img):
+        raise ValueError('nl_means: out must be a DeviceArray other than the (device) source')
+    ctx = _ctx_of(img, out, ctx=ctx)
+    d = img if dev else ctx.to_device(np.ascontiguousarray(img))
+    n, hh, ww = as_frames(d)
+    d_out = _dev_out(ctx, out, d.shape, d.dtype)
+    ctx._check(ctx._lib.ipa_nl_means_dev(
+        ctx.handle, d.ptr, dtype_id(d.dtype), n, hh, ww, ww, hh * ww, patch_size, patch_distance, h,
+        sigma, d_out.ptr, ww, hh * ww), 'nl_means')
+    return d_out if dev else d_out.get()
+
+
+def nan_to_zero(img):
+    """img[isnan(img)] = 0 in place on a float32 / float64 DeviceArray, (h, w) or (n, h, w)
+    (ipa_nan_to_zero_dev; camera/CameraCalibration.py:467).  Returns img."""
+    if not _is_dev(img) or img.dtype not in (np.float32, np.float64):
+        raise TypeError('nan_to_zero needs a float32 / float64 DeviceArray')
+    n, hh, ww = as_frames(img)
+    img.ctx._check(img.ctx._lib.ipa_nan_to_zero_dev(img.ctx.handle, img.ptr, dtype_id(img.dtype), n, hh,
+                                                    ww, ww, hh * ww), 'nan_to_zero')
+    return img
+
+
 # ------------------------------------------------- fused remap -> filter --
 def _fused_out(ctx, src, out, dh, dw, n):
     odt = np.float64 if src.dtype == np.float64 else np.float32

@@ -508,6 +508,31 @@ int ipa_ste_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int
 int ipa_remove_single_pixels_dev(ipa_ctx* ctx, const unsigned char* d_in, int h, int w, long pitch,
                                  unsigned char* d_out, long out_pitch);
 
+/* ---------------------------------------------------------------- denoising */
+/* replaces skimage.restoration.denoise_nl_means(image, patch_size, patch_distance, h,
+ * fast_mode=True, sigma=sigma) of scikit-image 0.18 (camera/CameraCalibration.py:461-474), with
+ * the exact exponential where that release uses its +-3 % fast_exp.  With s = patch_size (an even
+ * size is s + 1), o = s / 2, d = patch_distance and P the frame continued by numpy's `reflect`
+ * (no edge repeat, period 2 (n - 1), repeated where the pad exceeds the frame):
+ *   D(p, t) = max((sum_q (P[q] - P[q + t])^2 - 2 sigma^2 (s - 1)^2) / (s^2 h_cut^2), 0),
+ *             q over the (s - 1) x (s - 1) window at offsets -o + 1 ... +o from p in both axes
+ *   w(p, t) = D > 5 ? 0 : exp(-D),  w(p, 0) = 2
+ *   out[p]  = sum_t w P[p + t] / sum_t w,  t in [-d, d]^2,
+ *             evaluated as P[p] + sum_t w (P[p + t] - P[p]) / sum_t w
+ * IPA_F32 frames compute in float, IPA_F64 frames in double.  n frames (1 ... 65535) of h, w >= 2,
+ * `frame_stride` / `dst_frame_stride` elements apart; not in place (IPA_ERR_BAD_ARG when source
+ * and destination overlap).  Bounds (IPA_ERR_BAD_ARG beyond them, nothing launched):
+ *   2 <= patch_size <= 11, patch_distance >= 0, h_cut > 0, sigma >= 0, and the LDS tile
+ *   (rows + s - 2 + 2 d) * (64 + 2 d) * sizeof(element) <= 65536 bytes,
+ *   rows = 64 for IPA_F32 and 32 for IPA_F64
+ * which admits d <= 30 (float32) and d <= 20 (float64) at s = 7, and d <= 29 / 19 at s = 11. */
+int ipa_nl_means_dev(ipa_ctx* ctx, const void* d_src, int dtype, int n, int h, int w, long pitch,
+                     long frame_stride, int patch_size, int patch_distance, double h_cut, double sigma,
+                     void* d_dst, long dst_pitch, long dst_frame_stride);
+/* image[isnan(image)] = 0 (camera/CameraCalibration.py:467), in place, IPA_F32 / IPA_F64 */
+int ipa_nan_to_zero_dev(ipa_ctx* ctx, void* d_img, int dtype, int n, int h, int w, long pitch,
+                        long frame_stride);
+
 #ifdef __cplusplus
 }
 #endif
