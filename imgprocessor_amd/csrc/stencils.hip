@@ -17,6 +17,7 @@
 // coalesce in L1.  Accumulation is in double like the reference's numba code
 // (float64 coefficient tables, `val` promoted to float64).
 #include "common.hpp"
+#include "stencil_paths.hpp"
 
 namespace ipa {
 
@@ -901,7 +902,8 @@ int ipa_median_threshold_size_dev(ipa_ctx* ctx, const void* d_img, int dtype, in
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, threshold > 0, "threshold must be > 0 (the reference returns the input as is)");
   IPA_REQUIRE(ctx, size >= 1, "size must be >= 1");
-  if (size == 3)
+  const int path = median_threshold_path(dtype, size);
+  if (path == 1)
     return median_threshold_launch(ctx, d_img, dtype, nullptr, nullptr, false, h, w, pitch, 0, 0,
                                    threshold, cond_less, d_out, out_pitch, d_indices, idx_pitch);
   IPA_REQUIRE(ctx, d_img && d_out, "null pointer");
@@ -911,9 +913,8 @@ int ipa_median_threshold_size_dev(ipa_ctx* ctx, const void* d_img, int dtype, in
   IPA_REQUIRE(ctx, d_img != d_out, "the median cannot run in place");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "median threshold supports float32/float64 (got dtype %d)", dtype);
-  const size_t es = dtype == IPA_F32 ? 4 : 8;
-  const size_t lds = (size_t)(4 + size - 1) * ((64 + size - 1) | 1) * es;
-  if (lds > 64 * 1024)
+  const size_t lds = median_threshold_lds(dtype, size);
+  if (path == 0)
     IPA_UNSUPPORTED(ctx, "median threshold: a %dx%d window does not fit the LDS tile", size, size);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
@@ -947,7 +948,7 @@ int ipa_closest_distance_dev(ipa_ctx* ctx, const unsigned char* d_arr, int h, in
     IPA_UNSUPPORTED(ctx, "closest_distance writes uint16 or float64 (got dtype %d)", out_dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (ksize <= 254) {  // (row distances fit a byte; the distances go through the context workspace)
+  if (closest_distance_path(ksize) == 1) {  // (row distances fit a byte; the distances go through the context workspace)
     int rc = ipa_ws_reserve(ctx, (size_t)h * w);
     if (rc) return rc;
     unsigned char* g = (unsigned char*)ctx->ws;
@@ -986,8 +987,8 @@ int ipa_pos_intensity_unc_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h,
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   {
-    const size_t lds = (size_t)(2 * ksize + 1) * 256 * sizeof(double);
-    if (lds <= 60 * 1024) {
+    const size_t lds = pos_intensity_unc_lds(ksize);
+    if (pos_intensity_unc_path(dtype, ksize) == 1) {
       if (dtype == IPA_F32)
         hipLaunchKernelGGL((pos_intensity_unc_sep_kernel<float>), grid, block, lds, ctx->stream,
                            (const float*)d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize,
@@ -1032,7 +1033,7 @@ int ipa_masked_mean_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsign
     const int segs_x = (w + 63) / 64;
     const long segs = (long)segs_x * h;
     dim3 wgrid((unsigned)((segs + 3) / 4)), wblock(256);
-    const bool cols = ksize / 2 >= 1 && ksize / 2 <= 32;
+    const bool cols = masked_mean_fill_path(dtype, ksize) == 1;
     if (dtype == IPA_F32) {
       if (cols)
         hipLaunchKernelGGL((masked_mean_fill_cols_kernel<float>), wgrid, wblock, 0, ctx->stream,
@@ -1069,8 +1070,8 @@ int ipa_masked_median_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsi
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "masked_median supports float32/float64 (got dtype %d)", dtype);
   const int k = ksize / 2, cap = 4 * k * k;
-  const size_t lds = (size_t)4 * 2 * cap * (dtype == IPA_F32 ? 4 : 8);  // two buffers per wave
-  if (lds > 64 * 1024)
+  const size_t lds = masked_median_lds(dtype, ksize);  // two buffers per wave
+  if (masked_median_path(dtype, ksize) == 0)
     IPA_UNSUPPORTED(ctx, "masked_median: a %dx%d window does not fit the per-wave LDS buffers",
                     2 * k, 2 * k);
   const int segs_x = (w + 63) / 64;
@@ -1103,10 +1104,9 @@ int ipa_nan_max_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, int w, lo
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   {
-    const int k = ksize / 2, rb = 32;
-    const size_t esz = dtype == IPA_F32 ? 4 : 8;
-    const size_t lds = ((size_t)(rb + 2 * k) * (64 + 2 * k) + (size_t)(rb + 2 * k) * 64) * esz;
-    if (k >= 1 && lds <= 60 * 1024) {
+    const int k = ksize / 2, rb = kNanMaxRB;
+    const size_t lds = nan_max_sep_lds(dtype, ksize);
+    if (nan_max_path(dtype, ksize) == 1) {
       dim3 sgrid((w + 63) / 64, (h + rb - 1) / rb), sblock(256);
       if (dtype == IPA_F32)
         hipLaunchKernelGGL((nan_max_sep_kernel<float>), sgrid, sblock, lds, ctx->stream,
@@ -1143,9 +1143,8 @@ int ipa_conv_ydep_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
     IPA_UNSUPPORTED(ctx, "conv_ydep supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t esz = dtype == IPA_F32 ? 4 : 8;
-  const size_t lds = (size_t)(64 + k1 - 1) * (4 + k0 - 1) * esz;
-  if (lds <= 48 * 1024) {  // the window of a block fits in LDS: staged version
+  const size_t lds = conv_ydep_tile_lds(dtype, k0, k1);
+  if (conv_ydep_path(dtype, k0, k1) == 1) {  // the window of a block fits in LDS: staged version
     if (dtype == IPA_F32)
       hipLaunchKernelGGL((conv_ydep_tile_kernel<float>), grid, block, lds, ctx->stream,
                          (const float*)d_src, h, w, src_pitch, d_kernels, k0, k1, border_x,
@@ -1178,14 +1177,17 @@ int ipa_local_std_dev(ipa_ctx* ctx, const void* d_img, const void* d_blurred, in
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   const int hkx = ksize_x / 2, hky = ksize_y / 2;
+  const int path = local_std_path(dtype, ksize_x, ksize_y);
   // square windows up to 11: 256-px tiles, 4 pixels per lane (stencils_ydep.hip)
-  if (ipa_local_std_wave_launch(ctx, d_img, d_blurred, dtype, h, w, pitch, blurred_pitch, hkx, hky,
-                                d_out, out_pitch) == 0) {
+  if (path == 1) {
+    if (ipa_local_std_wave_launch(ctx, d_img, d_blurred, dtype, h, w, pitch, blurred_pitch, hkx,
+                                  hky, d_out, out_pitch) != 0)
+      IPA_UNSUPPORTED(ctx, "local_std: no wave kernel for half window %d", hkx);
     IPA_HIP(ctx, hipGetLastError());
     return IPA_OK;
   }
-  const size_t lds = (size_t)(64 + 2 * hky) * (4 + 2 * hkx) * (dtype == IPA_F32 ? 4 : 8);
-  if (lds <= 48 * 1024) {  // the block's window fits in LDS: staged version
+  const size_t lds = local_std_tile_lds(dtype, hkx, hky);
+  if (path == 2) {  // the block's window fits in LDS: staged version
     if (dtype == IPA_F32)
       hipLaunchKernelGGL((local_std_tile_kernel<float>), grid, block, lds, ctx->stream,
                          (const float*)d_img, (const float*)d_blurred, h, w, pitch, blurred_pitch,
@@ -1204,6 +1206,22 @@ int ipa_local_std_dev(ipa_ctx* ctx, const void* d_img, const void* d_blurred, in
                        ksize_x / 2, ksize_y / 2, (double*)d_out, out_pitch);
   IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
+}
+
+// which kernel an entry point above (and ipa_var_y_gauss_dev) launches: stencil_paths.hpp
+int ipa_stencil_path(int op, int dtype, int kx, int ky) {
+  switch (op) {
+    case IPA_STENCIL_LOCAL_STD: return local_std_path(dtype, kx, ky);
+    case IPA_STENCIL_MASKED_MEAN_FILL: return masked_mean_fill_path(dtype, kx);
+    case IPA_STENCIL_MASKED_MEDIAN: return masked_median_path(dtype, kx);
+    case IPA_STENCIL_NAN_MAX: return nan_max_path(dtype, kx);
+    case IPA_STENCIL_CLOSEST_DISTANCE: return closest_distance_path(kx);
+    case IPA_STENCIL_POS_INTENSITY_UNC: return pos_intensity_unc_path(dtype, kx);
+    case IPA_STENCIL_MEDIAN_THRESHOLD: return median_threshold_path(dtype, kx);
+    case IPA_STENCIL_VAR_Y_GAUSS: return var_y_gauss_plan_of(dtype, ky, kx).path;
+    case IPA_STENCIL_CONV_YDEP: return conv_ydep_path(dtype, ky, kx);
+  }
+  return -1;
 }
 
 }  // extern "C"

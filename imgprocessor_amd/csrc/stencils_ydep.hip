@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "stencil_paths.hpp"
 
 namespace ipa {
 
@@ -72,7 +73,7 @@ ydep_outer_kernel(const double* __restrict__ cols, const double* __restrict__ ro
   table[idx] = cols[rc] * rowk[idx - rc * kx];
 }
 
-constexpr int kYdepTW = 256;  // output pixels per workgroup row (4 per lane)
+// (kYdepTW = 256 output pixels per workgroup row, 4 per lane: stencil_paths.hpp)
 
 // K1 = kx when it is 1, 3 or 5 (window of a lane read once per tile row, loops unrolled),
 // 0 = any kx
@@ -292,12 +293,10 @@ static void local_std_wave_launch(ipa_ctx* ctx, const void* img, const void* blu
 
 using namespace ipa;
 
-// square windows of ksize 2..11 (hk = 1..5); 1 = not covered (the generic kernels of
-// stencils.hip run instead)
+// the square windows of local_std_path() == 1 (hk = 1..5)
 int ipa_local_std_wave_launch(ipa_ctx* ctx, const void* img, const void* blurred, int dtype, int h,
                               int w, long pitch, long bpitch, int hkx, int hky, void* out,
                               long opitch) {
-  if (hkx != hky || hkx < 1 || hkx > 5) return 1;
 #define IPA_STD_CASE(HK)                                                                          \
   case HK:                                                                                        \
     if (dtype == IPA_F32) local_std_wave_launch<float, HK>(ctx, img, blurred, h, w, pitch, bpitch, out, opitch); \
@@ -329,21 +328,11 @@ int ipa_var_y_gauss_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w
   IPA_REQUIRE(ctx, d_src != d_dst, "varYSizeGaussianFilter cannot run in place");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "varYSizeGaussianFilter supports float32/float64 (got dtype %d)", dtype);
-  const size_t esz = dtype == IPA_F32 ? 4 : 8;
-  // rows per workgroup: ~2 x the kernel height (read amplification <= 1.5) while the tile stays
-  // below ~30 KB (5 workgroups per CU), never above 60 KB
-  const int tw = kYdepTW + kx - 1 + 3;
-  auto lds_of = [&](int r) {
-    return (size_t)r * ky * 8 + (size_t)kx * 8 + (size_t)(r + ky - 1) * tw * esz;
-  };
-  int rb = 2 * ky < 16 ? 16 : (2 * ky + 3) / 4 * 4;
-  if (rb > 64) rb = 64;
-  while (rb > 8 && lds_of(rb) > 30 * 1024) rb -= 4;
-  while (rb > 4 && lds_of(rb) > 60 * 1024) rb -= 4;
-  // windows beyond the tile (stdyrange above ~23 for float32, ~11 for float64): the whole
-  // h x ky x kx table is expanded on the device and the generic entry point runs it - any
-  // stdyrange the reference accepts works, as before the tiled kernel existed
-  const bool tiled = lds_of(rb) <= 64 * 1024;
+  const size_t esz = stencil_esize(dtype);
+  // rows per workgroup and tiled / expanded: var_y_gauss_plan_of (stencil_paths.hpp)
+  const var_y_gauss_plan plan = var_y_gauss_plan_of(dtype, ky, kx);
+  const int rb = plan.rb;
+  const bool tiled = plan.path == 1;
   // tables in the context's plan scratch: cols (h * ky doubles) + rowk (kx doubles) [+ table]
   const size_t cols_b = (size_t)h * ky * sizeof(double);
   const size_t table_b = tiled ? 0 : cols_b * kx;
@@ -372,7 +361,7 @@ int ipa_var_y_gauss_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w
   const int vec_out = (((uintptr_t)d_dst) % 16 == 0) && ((dst_pitch * (long)esz) % 16 == 0);
   dim3 grid((w + kYdepTW - 1) / kYdepTW, (h + rb - 1) / rb), block(256);
 #define IPA_YDEP_LAUNCH(T, K1)                                                                 \
-  hipLaunchKernelGGL((conv_ydep_sep_kernel<T, K1>), grid, block, lds_of(rb), ctx->stream,         \
+  hipLaunchKernelGGL((conv_ydep_sep_kernel<T, K1>), grid, block, plan.lds, ctx->stream,           \
                      (const T*)d_src, h, w, src_pitch, d_cols, ky, d_rowk, kx, border_x, border_y, \
                      rb, (T*)d_dst, dst_pitch, vec_out)
   if (dtype == IPA_F32) {

@@ -254,7 +254,8 @@ int ipa_masked_mean_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsign
 /* replaces filters/maskedFilter.py:76-102 (_calcMedian, maskedFilter(fn='median')): as
  * ipa_masked_mean_dev with np.median of the window's mask == 0 pixels (mean of the two middle
  * values for an even count; NaN if any of them is NaN).  The window (ksize/2*2)^2 must fit the
- * kernel's per-wave LDS buffer: ksize <= 126 for float32, 90 for float64. */
+ * kernel's per-wave LDS buffers (two per wave, four waves, 64 KiB): ksize <= 45 for float32,
+ * 33 for float64; IPA_ERR_UNSUPPORTED beyond, d_out untouched. */
 int ipa_masked_median_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsigned char* d_mask,
                           int h, int w, long pitch, long mask_pitch, int ksize, int fill_mask,
                           void* d_out, long out_pitch);
@@ -306,6 +307,24 @@ int ipa_median_threshold_size_dev(ipa_ctx* ctx, const void* d_img, int dtype, in
 int ipa_calib_prefilter_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_bg,
                             const void* d_ff, int h, int w, long pitch, long bg_pitch,
                             long ff_pitch, double threshold, void* d_out, long out_pitch);
+
+/* Which kernel an entry point of this section launches for a window and dtype: the launchers'
+ * own selection arithmetic (csrc/stencil_paths.hpp), without a context or a device.  Returns
+ * 0 = refused, 1.. = the kernels in the order listed, -1 = unknown op.  kx / ky as below. */
+typedef enum {
+  IPA_STENCIL_LOCAL_STD = 0,         /* kx, ky = ksize_x, ksize_y: 1 wave (square, half window
+                                        1..5), 2 LDS tile, 3 generic */
+  IPA_STENCIL_MASKED_MEAN_FILL = 1,  /* kx = ksize, in place: 1 column sums, 2 wave */
+  IPA_STENCIL_MASKED_MEDIAN = 2,     /* kx = ksize: 1 wave kernel, 0 refused */
+  IPA_STENCIL_NAN_MAX = 3,           /* kx = ksize: 1 separable LDS, 2 generic */
+  IPA_STENCIL_CLOSEST_DISTANCE = 4,  /* kx = ksize: 1 two-pass row distances, 2 direct */
+  IPA_STENCIL_POS_INTENSITY_UNC = 5, /* kx = ksize (half window): 1 separable, 2 generic */
+  IPA_STENCIL_MEDIAN_THRESHOLD = 6,  /* kx = size: 1 3x3 network, 2 counting, 0 refused */
+  IPA_STENCIL_VAR_Y_GAUSS = 7,       /* kx, ky = taps along x, y: 1 tiled, 2 expanded table
+                                        through the conv_ydep tile kernel, 3 ... generic */
+  IPA_STENCIL_CONV_YDEP = 8          /* kx, ky = k1, k0: 1 LDS tile, 2 generic */
+} ipa_stencil_op;
+int ipa_stencil_path(int op, int dtype, int kx, int ky);
 
 /* replaces filters/_extendArrayForConvolution.py:5-97 for callers that want the
  * padded array itself (the filters above resolve borders while staging and do
