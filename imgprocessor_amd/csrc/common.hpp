@@ -157,6 +157,11 @@ struct ipa_event {
 
 void ipa_set_error(ipa_ctx* ctx, const char* fmt, ...);
 int ipa_ws_reserve(ipa_ctx* ctx, size_t bytes);                         // ctx->ws >= bytes
+// the host-pointer fills (idw.hip, interp_more.hip): grid and mask (never null: the callers refuse
+// that, each in its own words) staged through ctx->ws; then the grid copied back and the stream drained
+int ipa_fill_stage(ipa_ctx* ctx, const void* grid, int dtype, const uint8_t* mask, int h, int w,
+                   char** d_grid, uint8_t** d_mask, size_t* grid_bytes);
+int ipa_fill_back(ipa_ctx* ctx, void* grid, const char* d_grid, size_t grid_bytes);
 int ipa_lens_map_cached(ipa_ctx* ctx, const double* K, const double* dist5, const double* newK,
                         int h, int w, float** mx, float** my);
 // remap.hip -> fused.hip: the strip remap of integer frames into their own type (1: not a call it covers)

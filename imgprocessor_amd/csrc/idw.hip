@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "common.hpp"
+#include "launch.hpp"
+#include "stencil_paths.hpp"
 
 namespace ipa {
 
@@ -168,19 +170,14 @@ int ipa_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t* d_mas
   int segs_x = (w + 63) / 64;
   long segs = (long)segs_x * h;
   dim3 grid((unsigned)((segs + 3) / 4)), block(256);
-  const int kw = 2 * ksize + 1;
-  const bool rows = kw > 16 && kw <= 64;
-#define IPA_IDW(T, R)                                                                          \
-  hipLaunchKernelGGL((idw_kernel<T, R>), grid, block, 0, ctx->stream, (T*)d_grid, d_mask, h, w, \
-                     pitch, ksize, (const double*)dw, segs_x)
-  if (dtype == IPA_F32) {
-    if (rows) IPA_IDW(float, true); else IPA_IDW(float, false);
-  } else {
-    if (rows) IPA_IDW(double, true); else IPA_IDW(double, false);
-  }
-#undef IPA_IDW
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  const bool rows = idw_path(dtype, ksize) == 2;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick<true, false>(rows, [&](auto R) {
+      return launch(ctx, idw_kernel<T, R()>, grid, block, 0, d_grid, d_mask, h, w, pitch, ksize, dw,
+                    segs_x);
+    });
+  });
 }
 
 int ipa_fast_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t* d_mask, int h,
@@ -203,56 +200,34 @@ int ipa_fast_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t* 
   int segs_x = (w + 63) / 64;
   long segs = (long)segs_x * h;
   dim3 grid((unsigned)((segs + 3) / 4)), block(256);
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL((fast_idw_kernel<float>), grid, block, 0, ctx->stream, (float*)d_grid,
-                       d_mask, h, w, pitch, doff, dwt, n, minnvals, segs_x);
-  else
-    hipLaunchKernelGGL((fast_idw_kernel<double>), grid, block, 0, ctx->stream, (double*)d_grid,
-                       d_mask, h, w, pitch, doff, dwt, n, minnvals, segs_x);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
-}
-
-static int idw_host(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
-                    char** d_grid, uint8_t** d_mask, size_t* gb) {
-  IPA_REQUIRE(ctx, grid && mask && h > 0 && w > 0, "bad arguments");
-  size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  *gb = (size_t)h * w * es;
-  int rc = ipa_ws_reserve(ctx, up(*gb) + up((size_t)h * w));
-  if (rc) return rc;
-  *d_grid = (char*)ctx->ws;
-  *d_mask = (uint8_t*)(*d_grid + up(*gb));
-  IPA_HIP(ctx, hipMemcpyAsync(*d_grid, grid, *gb, hipMemcpyHostToDevice, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(*d_mask, mask, (size_t)h * w, hipMemcpyHostToDevice, ctx->stream));
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    return launch(ctx, fast_idw_kernel<decltype(t)>, grid, block, 0, d_grid, d_mask, h, w, pitch,
+                  doff, dwt, n, minnvals, segs_x);
+  });
 }
 
 int ipa_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
                  int ksize, const double* weights) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  IPA_REQUIRE(ctx, mask, "bad arguments");
   char* dg; uint8_t* dm; size_t gb;
-  int rc = idw_host(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
   if (rc) return rc;
   rc = ipa_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, weights);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(grid, dg, gb, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_fill_back(ctx, grid, dg, gb);
 }
 
 int ipa_fast_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
                       const int32_t* offsets, const double* weights, int n, int minnvals) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  IPA_REQUIRE(ctx, mask, "bad arguments");
   char* dg; uint8_t* dm; size_t gb;
-  int rc = idw_host(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
   if (rc) return rc;
   rc = ipa_fast_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, offsets, weights, n, minnvals);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(grid, dg, gb, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_fill_back(ctx, grid, dg, gb);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 // the reference's float64 expressions operation for operation: no fused multiply-add (hipcc
 // contracts by default; the __dmul_rn / __dadd_rn intrinsics do not help - they are inline
@@ -476,17 +477,13 @@ int ipa_unstructured_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, int h, int w
   if (rc) return rc;
   dim3 grid((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)), block(256);
   const int pw = power == 2.0 ? 2 : (power == 1.0 ? 1 : 0);
-#define IPA_UIDW(T, PW)                                                                        \
-  hipLaunchKernelGGL((unstructured_idw_kernel<T, PW>), grid, block, 0, ctx->stream, (T*)d_grid, \
-                     h, w, pitch, (const double*)d, n, 0.5 * power)
-  if (dtype == IPA_F32) {
-    if (pw == 2) IPA_UIDW(float, 2); else if (pw == 1) IPA_UIDW(float, 1); else IPA_UIDW(float, 0);
-  } else {
-    if (pw == 2) IPA_UIDW(double, 2); else if (pw == 1) IPA_UIDW(double, 1); else IPA_UIDW(double, 0);
-  }
-#undef IPA_UIDW
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick_or_last<2, 1, 0>(pw, [&](auto PW) {
+      return launch(ctx, unstructured_idw_kernel<T, PW()>, grid, block, 0, d_grid, h, w, pitch, d, n,
+                    0.5 * power);
+    });
+  });
 }
 
 int ipa_circular_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t* d_mask, int h,
@@ -507,19 +504,16 @@ int ipa_circular_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8
   int rc = ipa_plan_reserve(ctx, (size_t)h * h * sizeof(double2));
   if (rc) return rc;
   double2* polar = (double2*)ctx->plan;
-  hipLaunchKernelGGL(polar_table_kernel, dim3((unsigned)((h + 255) / 256), (unsigned)h), block, 0,
-                     ctx->stream, h, cx, cy, polar);
-#define IPA_CIDW(T, PW)                                                                          \
-  hipLaunchKernelGGL((circular_idw_kernel<T, PW>), grid, block, 0, ctx->stream, (T*)d_grid, d_mask, \
-                     h, w, pitch, ksize, 0.5 * power, fr, fphi, cx, cy, segs_x, polar)
-  if (dtype == IPA_F32) {
-    if (pw == 2) IPA_CIDW(float, 2); else if (pw == 1) IPA_CIDW(float, 1); else IPA_CIDW(float, 0);
-  } else {
-    if (pw == 2) IPA_CIDW(double, 2); else if (pw == 1) IPA_CIDW(double, 1); else IPA_CIDW(double, 0);
-  }
-#undef IPA_CIDW
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  rc = launch(ctx, polar_table_kernel, dim3((unsigned)((h + 255) / 256), (unsigned)h), block, 0, h, cx,
+              cy, polar);
+  if (rc) return rc;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick_or_last<2, 1, 0>(pw, [&](auto PW) {
+      return launch(ctx, circular_idw_kernel<T, PW()>, grid, block, 0, d_grid, d_mask, h, w, pitch,
+                    ksize, 0.5 * power, fr, fphi, cx, cy, segs_x, polar);
+    });
+  });
 }
 
 int ipa_cross_avg_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t* d_mask, int h,
@@ -534,54 +528,29 @@ int ipa_cross_avg_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t*
   const size_t avg_b = up((size_t)h * w * es), row_b = up((size_t)h * 4);
   int rc = ipa_plan_reserve(ctx, avg_b + 2 * row_b);
   if (rc) return rc;
-  char* avg = (char*)ctx->plan;
-  int* rowlast = (int*)(avg + avg_b);
-  int* prev = (int*)(avg + avg_b + row_b);
+  void* avg = ctx->plan;
+  int* rowlast = (int*)((char*)avg + avg_b);
+  int* prev = (int*)((char*)avg + avg_b + row_b);
   const int segs_x = (w + kCrossSeg - 1) / kCrossSeg;
   const long segs = (long)segs_x * h;
   dim3 grid((unsigned)((segs + 3) / 4)), block(256);
-  hipLaunchKernelGGL(cross_row_last_kernel, dim3((unsigned)((h + 3) / 4)), block, 0, ctx->stream,
-                     d_mask, h, w, rowlast);
-  hipLaunchKernelGGL(cross_prev_row_kernel, dim3(1), dim3(64), 0, ctx->stream, rowlast, h, prev);
-  if (dtype == IPA_F32) {
-    hipLaunchKernelGGL((cross_local_avg_kernel<float>), grid, block, 0, ctx->stream,
-                       (const float*)d_grid, d_mask, h, w, pitch, ksize, (float*)avg, segs_x);
-    hipLaunchKernelGGL((cross_fill_kernel<float>), grid, block, 0, ctx->stream, (float*)d_grid,
-                       d_mask, h, w, pitch, 0.5 * power, (const float*)avg, rowlast, prev, segs_x);
-  } else {
-    hipLaunchKernelGGL((cross_local_avg_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_grid, d_mask, h, w, pitch, ksize, (double*)avg, segs_x);
-    hipLaunchKernelGGL((cross_fill_kernel<double>), grid, block, 0, ctx->stream, (double*)d_grid,
-                       d_mask, h, w, pitch, 0.5 * power, (const double*)avg, rowlast, prev, segs_x);
-  }
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  rc = launch(ctx, cross_row_last_kernel, dim3((unsigned)((h + 3) / 4)), block, 0, d_mask, h, w,
+              rowlast);
+  if (rc) return rc;
+  rc = launch(ctx, cross_prev_row_kernel, dim3(1), dim3(64), 0, rowlast, h, prev);
+  if (rc) return rc;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    const int st = launch(ctx, cross_local_avg_kernel<T>, grid, block, 0, d_grid, d_mask, h, w, pitch,
+                          ksize, avg, segs_x);
+    if (st) return st;
+    return launch(ctx, cross_fill_kernel<T>, grid, block, 0, d_grid, d_mask, h, w, pitch,
+                  0.5 * power, avg, rowlast, prev, segs_x);
+  });
 }
 
 // host-pointer forms: grid (and mask) staged through the context's workspace
-static int fill_host(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
-                     char** d_grid, uint8_t** d_mask, size_t* gb) {
-  IPA_REQUIRE(ctx, grid && h > 0 && w > 0, "bad arguments");
-  const size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  *gb = (size_t)h * w * es;
-  int rc = ipa_ws_reserve(ctx, up(*gb) + up((size_t)h * w));
-  if (rc) return rc;
-  *d_grid = (char*)ctx->ws;
-  *d_mask = (uint8_t*)(*d_grid + up(*gb));
-  IPA_HIP(ctx, hipMemcpyAsync(*d_grid, grid, *gb, hipMemcpyHostToDevice, ctx->stream));
-  if (mask)
-    IPA_HIP(ctx, hipMemcpyAsync(*d_mask, mask, (size_t)h * w, hipMemcpyHostToDevice, ctx->stream));
-  return IPA_OK;
-}
-
-static int fill_back(ipa_ctx* ctx, void* grid, const char* dg, size_t gb) {
-  IPA_HIP(ctx, hipMemcpyAsync(grid, dg, gb, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
-}
-
+// (ipa_fill_stage / ipa_fill_back, runtime.hip)
 int ipa_unstructured_idw(ipa_ctx* ctx, void* grid, int dtype, int h, int w, const double* x,
                          const double* y, const double* v, int n, double power) {
   if (!ctx) return IPA_ERR_BAD_ARG;
@@ -593,7 +562,7 @@ int ipa_unstructured_idw(ipa_ctx* ctx, void* grid, int dtype, int h, int w, cons
   if (rc) return rc;
   rc = ipa_unstructured_idw_dev(ctx, ctx->ws, dtype, h, w, w, x, y, v, n, power);
   if (rc) return rc;
-  return fill_back(ctx, grid, (const char*)ctx->ws, gb);
+  return ipa_fill_back(ctx, grid, (const char*)ctx->ws, gb);
 }
 
 int ipa_circular_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
@@ -601,11 +570,11 @@ int ipa_circular_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* ma
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
   char* dg; uint8_t* dm; size_t gb;
-  int rc = fill_host(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
   if (rc) return rc;
   rc = ipa_circular_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, power, fr, fphi, cx, cy);
   if (rc) return rc;
-  return fill_back(ctx, grid, dg, gb);
+  return ipa_fill_back(ctx, grid, dg, gb);
 }
 
 int ipa_cross_avg_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
@@ -613,11 +582,11 @@ int ipa_cross_avg_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask,
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
   char* dg; uint8_t* dm; size_t gb;
-  int rc = fill_host(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
   if (rc) return rc;
   rc = ipa_cross_avg_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, power);
   if (rc) return rc;
-  return fill_back(ctx, grid, dg, gb);
+  return ipa_fill_back(ctx, grid, dg, gb);
 }
 
 int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_mask, int h, int w,
@@ -638,30 +607,26 @@ int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_m
   IPA_HIP(ctx, hipMemsetAsync(border, 0, bb + 256, ctx->stream));
   const unsigned nb = (unsigned)(((long)h * w + 255) / 256);
   const double hp = 0.5 * power;
+  const int pw = power == 2.0 ? 2 : (power == 1.0 ? 1 : 0);
   const size_t lds = (size_t)h * sizeof(int);
   for (long n = 0;; n++) {
     // _createBorder; its return value decides whether another sweep runs
-    hipLaunchKernelGGL(ps_border_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_mask, border, h, w, any);
+    rc = launch(ctx, ps_border_kernel, dim3(nb), dim3(256), 0, d_mask, border, h, w, any);
+    if (rc) return rc;
     unsigned found = 0;
     IPA_HIP(ctx, hipMemcpyAsync(&found, any, sizeof(found), hipMemcpyDeviceToHost, ctx->stream));
     IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!found || n >= max_iter) break;
     IPA_HIP(ctx, hipMemsetAsync(any, 0, sizeof(unsigned), ctx->stream));
-#define IPA_PS_LAUNCH(T, PW)                                                                     \
-  hipLaunchKernelGGL((ps_sweep_kernel<T, PW>), dim3(1), dim3(1024), lds, ctx->stream, (T*)d_grid, \
-                     d_mask, border, h, w, pitch, ksize, hp)
-    if (dtype == IPA_F32) {
-      if (power == 2.0) IPA_PS_LAUNCH(float, 2);
-      else if (power == 1.0) IPA_PS_LAUNCH(float, 1);
-      else IPA_PS_LAUNCH(float, 0);
-    } else {
-      if (power == 2.0) IPA_PS_LAUNCH(double, 2);
-      else if (power == 1.0) IPA_PS_LAUNCH(double, 1);
-      else IPA_PS_LAUNCH(double, 0);
-    }
-#undef IPA_PS_LAUNCH
+    rc = by_float(dtype, [&](auto t) {
+      using T = decltype(t);
+      return pick_or_last<2, 1, 0>(pw, [&](auto PW) {
+        return launch(ctx, ps_sweep_kernel<T, PW()>, dim3(1), dim3(1024), lds, d_grid, d_mask, border,
+                      h, w, pitch, ksize, hp);
+      });
+    });
+    if (rc) return rc;
   }
-  IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
 }
 
@@ -670,13 +635,13 @@ int ipa_point_spread_idw(ipa_ctx* ctx, void* grid, int dtype, uint8_t* mask, int
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
   char* dg; uint8_t* dm; size_t gb;
-  int rc = fill_host(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
   if (rc) return rc;
   rc = ipa_point_spread_idw_dev(ctx, dg, dtype, dm, h, w, w, ksize, power, max_iter);
   if (rc) return rc;
   // the mask is modified too (filled pixels are unmasked)
   IPA_HIP(ctx, hipMemcpyAsync(mask, dm, (size_t)h * w, hipMemcpyDeviceToHost, ctx->stream));
-  return fill_back(ctx, grid, dg, gb);
+  return ipa_fill_back(ctx, grid, dg, gb);
 }
 
 }  // extern "C"

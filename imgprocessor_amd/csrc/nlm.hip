@@ -23,6 +23,7 @@
 // P[p] + sum w (P[p + t] - P[p]) / sum w with one division: the weighted mean, exact where every
 // surviving neighbour equals the pixel (a constant image, a cut-off only the self pair passes).
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace ipa {
 namespace {
@@ -240,15 +241,10 @@ int ipa_nan_to_zero_dev(ipa_ctx* ctx, void* d_img, int dtype, int n, int h, int 
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "nan_to_zero: frames are float32 / float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4, n), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL(nan_to_zero_kernel<float>, grid, block, 0, ctx->stream, (float*)d_img, h, w, pitch,
-                       frame_stride);
-  else
-    hipLaunchKernelGGL(nan_to_zero_kernel<double>, grid, block, 0, ctx->stream, (double*)d_img, h, w, pitch,
-                       frame_stride);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    return launch(ctx, nan_to_zero_kernel<decltype(t)>, grid, block, 0, d_img, h, w, pitch,
+                  frame_stride);
+  });
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 #define IPA_NO_FMA _Pragma("clang fp contract(off)")
 
@@ -315,24 +316,20 @@ static void area_tables(int ssize, int dsize, double scale, std::vector<AreaTab>
 }
 
 template <typename T>
-static void launch_separable(ipa_ctx* ctx, int ks, const T* src, long spitch, int sh, int sw, T* tmp,
-                             T* dst, long dpitch, int dh, int dw, const int* xofs,
-                             const float* alpha, int xmax, const int* yofs, const float* beta) {
+static int launch_separable(ipa_ctx* ctx, int ks, const void* src, long spitch, int sh, int sw, void* tmp,
+                            void* dst, long dpitch, int dh, int dw, const int* xofs,
+                            const float* alpha, int xmax, const int* yofs, const float* beta) {
   dim3 block(256), gh((unsigned)((dw + 255) / 256), (unsigned)sh), gv((unsigned)((dw + 255) / 256), (unsigned)dh);
   dim3 gv4((unsigned)((dw / 4 + 255) / 256), (unsigned)dh);
   const bool vec4 = dw % 4 == 0 && dpitch % 4 == 0 && (uintptr_t)dst % (4 * sizeof(T)) == 0 &&
                     (uintptr_t)tmp % (4 * sizeof(T)) == 0;
-#define IPA_RS(KS)                                                                                 \
-  hipLaunchKernelGGL((hresize_kernel<T, KS>), gh, block, 0, ctx->stream, src, spitch, sh, sw, tmp,  \
-                     dw, xofs, alpha, xmax);                                                        \
-  if (vec4)                                                                                        \
-    hipLaunchKernelGGL((vresize4_kernel<T, KS>), gv4, block, 0, ctx->stream, (const T*)tmp, sh, dw,  \
-                       dst, dpitch, yofs, beta);                                                    \
-  else                                                                                             \
-    hipLaunchKernelGGL((vresize_kernel<T, KS>), gv, block, 0, ctx->stream, (const T*)tmp, sh, dw,   \
-                       dst, dpitch, yofs, beta)
-  if (ks == 2) { IPA_RS(2); } else if (ks == 4) { IPA_RS(4); } else { IPA_RS(8); }
-#undef IPA_RS
+  return pick_or_last<2, 4, 8>(ks, [&](auto KS) {
+    const int rc = launch(ctx, hresize_kernel<T, KS()>, gh, block, 0, src, spitch, sh, sw, tmp, dw,
+                          xofs, alpha, xmax);
+    if (rc) return rc;
+    return launch(ctx, vec4 ? vresize4_kernel<T, KS()> : vresize_kernel<T, KS()>, vec4 ? gv4 : gv,
+                  block, 0, tmp, sh, dw, dst, dpitch, yofs, beta);
+  });
 }
 
 }  // namespace ipa
@@ -353,7 +350,6 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
   const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
   const size_t es = ipa_dtype_size(dtype);
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
   dim3 block(256), grid((unsigned)((dw + 255) / 256), (unsigned)dh);
   // OpenCV's rule (resize.cpp): INTER_LINEAR at an exact 2 x 2 reduction IS the area average
   // ("interpolation == INTER_LINEAR && is_area_fast && iscale_x == 2 && iscale_y == 2")
@@ -368,16 +364,10 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
                            "variant when enlarging)");
     const int isx = (int)nearbyint(scale_x), isy = (int)nearbyint(scale_y);
     if (fabs(scale_x - isx) < DBL_EPSILON && fabs(scale_y - isy) < DBL_EPSILON) {
-      if (dtype == IPA_F32)
-        hipLaunchKernelGGL((area_fast_kernel<float>), grid, block, 0, ctx->stream,
-                           (const float*)d_src, src_pitch, sh, sw, (float*)d_dst, dst_pitch, dh, dw,
-                           isx, isy);
-      else
-        hipLaunchKernelGGL((area_fast_kernel<double>), grid, block, 0, ctx->stream,
-                           (const double*)d_src, src_pitch, sh, sw, (double*)d_dst, dst_pitch, dh,
-                           dw, isx, isy);
-      IPA_HIP(ctx, hipGetLastError());
-      return IPA_OK;
+      return by_float(dtype, [&](auto t) {
+        return launch(ctx, area_fast_kernel<decltype(t)>, grid, block, 0, d_src, src_pitch, sh, sw,
+                      d_dst, dst_pitch, dh, dw, isx, isy);
+      });
     }
     std::vector<AreaTab> xt, yt;
     std::vector<int> xs, ys;
@@ -393,19 +383,12 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
     void* d = nullptr;
     int rc = ipa_tab_upload(ctx, blob.data(), blob.size(), &d);
     if (rc) return rc;
-    const char* t = (const char*)d;
-    if (dtype == IPA_F32)
-      hipLaunchKernelGGL((area_kernel<float>), grid, block, 0, ctx->stream, (const float*)d_src,
-                         src_pitch, (float*)d_dst, dst_pitch, dw, (const AreaTab*)t,
-                         (const int*)(t + b0), (const AreaTab*)(t + b0 + b1),
-                         (const int*)(t + b0 + b1 + b2));
-    else
-      hipLaunchKernelGGL((area_kernel<double>), grid, block, 0, ctx->stream, (const double*)d_src,
-                         src_pitch, (double*)d_dst, dst_pitch, dw, (const AreaTab*)t,
-                         (const int*)(t + b0), (const AreaTab*)(t + b0 + b1),
-                         (const int*)(t + b0 + b1 + b2));
-    IPA_HIP(ctx, hipGetLastError());
-    return IPA_OK;
+    const char* tab = (const char*)d;
+    return by_float(dtype, [&](auto t) {
+      return launch(ctx, area_kernel<decltype(t)>, grid, block, 0, d_src, src_pitch, d_dst, dst_pitch,
+                    dw, (const AreaTab*)tab, (const int*)(tab + b0), (const AreaTab*)(tab + b0 + b1),
+                    (const int*)(tab + b0 + b1 + b2));
+    });
   }
   if (interp != IPA_RESIZE_LINEAR && interp != IPA_RESIZE_CUBIC && interp != IPA_RESIZE_LANCZOS4)
     IPA_UNSUPPORTED(ctx, "resize: interpolation %d (INTER_LINEAR 1, INTER_CUBIC 2, INTER_AREA 3, "
@@ -443,17 +426,11 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
   rc = ipa_plan_reserve(ctx, (size_t)sh * dw * es);   // the horizontally resized rows
   if (rc) return rc;
   const char* t = (const char*)d;
-  if (dtype == IPA_F32)
-    launch_separable<float>(ctx, ks, (const float*)d_src, src_pitch, sh, sw, (float*)ctx->plan,
-                            (float*)d_dst, dst_pitch, dh, dw, (const int*)t, (const float*)(t + b0),
-                            xmax, (const int*)(t + b0 + b1), (const float*)(t + b0 + b1 + b2));
-  else
-    launch_separable<double>(ctx, ks, (const double*)d_src, src_pitch, sh, sw, (double*)ctx->plan,
-                             (double*)d_dst, dst_pitch, dh, dw, (const int*)t,
-                             (const float*)(t + b0), xmax, (const int*)(t + b0 + b1),
-                             (const float*)(t + b0 + b1 + b2));
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto f) {
+    return launch_separable<decltype(f)>(ctx, ks, d_src, src_pitch, sh, sw, ctx->plan, d_dst, dst_pitch,
+                                         dh, dw, (const int*)t, (const float*)(t + b0), xmax,
+                                         (const int*)(t + b0 + b1), (const float*)(t + b0 + b1 + b2));
+  });
 }
 
 int ipa_resize(ipa_ctx* ctx, const void* src, int dtype, int sh, int sw, void* dst, int dh, int dw,
@@ -490,16 +467,11 @@ int ipa_fast_filter_stat_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, 
                          "LDS (raise `every`)", per_axis, per_axis, kStatMax);
   const int n0 = (h + every - 1) / every, n1 = (w + every - 1) / every;
   IPA_REQUIRE(ctx, n0 <= 65535, "too many rows of cells");
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
   dim3 grid((unsigned)n1, (unsigned)n0), block(64);
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL((fast_filter_stat_kernel<float>), grid, block, 0, ctx->stream,
-                       (const float*)d_arr, pitch, h, w, ksize, every, fn, d_out, n1);
-  else
-    hipLaunchKernelGGL((fast_filter_stat_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_arr, pitch, h, w, ksize, every, fn, d_out, n1);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    return launch(ctx, fast_filter_stat_kernel<decltype(t)>, grid, block, 0, d_arr, pitch, h, w, ksize,
+                  every, fn, d_out, n1);
+  });
 }
 
 int ipa_fast_filter_stat(ipa_ctx* ctx, const void* arr, int dtype, int h, int w, int ksize,

@@ -361,6 +361,29 @@ int ipa_ws_reserve(ipa_ctx* c, size_t bytes) {
   return IPA_OK;
 }
 
+int ipa_fill_stage(ipa_ctx* ctx, const void* grid, int dtype, const uint8_t* mask, int h, int w,
+                   char** d_grid, uint8_t** d_mask, size_t* gb) {
+  IPA_REQUIRE(ctx, grid && h > 0 && w > 0, "bad arguments");
+  const size_t es = ipa_dtype_size(dtype);
+  IPA_REQUIRE(ctx, es, "unknown dtype");
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  *gb = (size_t)h * w * es;
+  int rc = ipa_ws_reserve(ctx, up(*gb) + up((size_t)h * w));
+  if (rc) return rc;
+  IPA_HIP(ctx, hipSetDevice(ctx->device));  // the reservation selects it only when it grows
+  *d_grid = (char*)ctx->ws;
+  *d_mask = (uint8_t*)(*d_grid + up(*gb));
+  IPA_HIP(ctx, hipMemcpyAsync(*d_grid, grid, *gb, hipMemcpyHostToDevice, ctx->stream));
+  IPA_HIP(ctx, hipMemcpyAsync(*d_mask, mask, (size_t)h * w, hipMemcpyHostToDevice, ctx->stream));
+  return IPA_OK;
+}
+
+int ipa_fill_back(ipa_ctx* ctx, void* grid, const char* d_grid, size_t gb) {
+  IPA_HIP(ctx, hipMemcpyAsync(grid, d_grid, gb, hipMemcpyDeviceToHost, ctx->stream));
+  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return IPA_OK;
+}
+
 int ipa_plan_reserve(ipa_ctx* c, size_t bytes) {
   c->plan_key_n = 0;  // the caller overwrites the buffer
   if (c->plan_bytes >= bytes) return IPA_OK;

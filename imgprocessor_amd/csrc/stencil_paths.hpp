@@ -89,6 +89,14 @@ static inline int conv_ydep_path(int dtype, int k0, int k1) {
   return conv_ydep_tile_lds(dtype, k0, k1) <= 48 * 1024 ? 1 : 2;
 }
 
+// ipa_idw_fill_dev (idw.hip; not among ipa_stencil_path's ops).  ksize = HALF window.
+// 1 = lanes over the taps, 2 = lanes over the columns of a window row (windows 17..64 wide)
+static inline int idw_path(int dtype, int ksize) {
+  if (!stencil_float(dtype) || ksize < 1 || ksize > 512) return 0;
+  const int kw = 2 * ksize + 1;
+  return kw > 16 && kw <= 64 ? 2 : 1;
+}
+
 // ipa_var_y_gauss_dev: 1 = tiled kernel (256 px x rb rows per workgroup), else the h x ky x kx
 // table is expanded and ipa_conv_ydep_dev runs it: 2 = through its tile kernel, 3 = generic
 constexpr int kYdepTW = 256;  // output pixels per workgroup row (4 per lane)

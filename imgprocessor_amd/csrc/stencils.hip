@@ -17,6 +17,7 @@
 // coalesce in L1.  Accumulation is in double like the reference's numba code
 // (float64 coefficient tables, `val` promoted to float64).
 #include "common.hpp"
+#include "launch.hpp"
 #include "stencil_paths.hpp"
 
 namespace ipa {
@@ -851,10 +852,6 @@ median_threshold_any_kernel(const T* __restrict__ img, int h, int w, long pitch,
 
 using namespace ipa;
 
-int ipa_local_std_wave_launch(ipa_ctx* ctx, const void* img, const void* blurred, int dtype, int h,
-                              int w, long pitch, long bpitch, int hkx, int hky, void* out,
-                              long opitch);  // stencils_ydep.hip
-
 extern "C" {
 
 static int median_threshold_launch(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_bg,
@@ -871,19 +868,14 @@ static int median_threshold_launch(ipa_ctx* ctx, const void* d_img, int dtype, c
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "median threshold supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-#define IPA_MT(T, CALIB)                                                                        \
-  hipLaunchKernelGGL((median_threshold_kernel<T, CALIB>), grid, block, 0, ctx->stream,          \
-                     (const T*)d_img, (const T*)d_bg, (const T*)d_ff, h, w, pitch, bg_pitch,     \
-                     ff_pitch, threshold, cond_less, (T*)d_out, out_pitch, d_indices, idx_pitch)
-  if (dtype == IPA_F32) {
-    if (calib) IPA_MT(float, true); else IPA_MT(float, false);
-  } else {
-    if (calib) IPA_MT(double, true); else IPA_MT(double, false);
-  }
-#undef IPA_MT
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick<true, false>(calib, [&](auto CALIB) {
+      return launch(ctx, median_threshold_kernel<T, CALIB()>, grid, block, 0, d_img, d_bg, d_ff, h,
+                    w, pitch, bg_pitch, ff_pitch, threshold, cond_less, d_out, out_pitch, d_indices,
+                    idx_pitch);
+    });
+  });
 }
 
 int ipa_median_threshold_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
@@ -917,17 +909,10 @@ int ipa_median_threshold_size_dev(ipa_ctx* ctx, const void* d_img, int dtype, in
   if (path == 0)
     IPA_UNSUPPORTED(ctx, "median threshold: a %dx%d window does not fit the LDS tile", size, size);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL((median_threshold_any_kernel<float>), grid, block, lds, ctx->stream,
-                       (const float*)d_img, h, w, pitch, size, threshold, cond_less, (float*)d_out,
-                       out_pitch, d_indices, idx_pitch);
-  else
-    hipLaunchKernelGGL((median_threshold_any_kernel<double>), grid, block, lds, ctx->stream,
-                       (const double*)d_img, h, w, pitch, size, threshold, cond_less,
-                       (double*)d_out, out_pitch, d_indices, idx_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    return launch(ctx, median_threshold_any_kernel<decltype(t)>, grid, block, lds, d_img, h, w,
+                  pitch, size, threshold, cond_less, d_out, out_pitch, d_indices, idx_pitch);
+  });
 }
 
 int ipa_calib_prefilter_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_bg,
@@ -947,30 +932,23 @@ int ipa_closest_distance_dev(ipa_ctx* ctx, const unsigned char* d_arr, int h, in
   if (out_dtype != IPA_U16 && out_dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "closest_distance writes uint16 or float64 (got dtype %d)", out_dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
+  // the output type: uint16 or float64
+  auto by_out = [&](auto&& f) { return out_dtype == IPA_U16 ? f((unsigned short)0) : f(double{}); };
   if (closest_distance_path(ksize) == 1) {  // (row distances fit a byte; the distances go through the context workspace)
     int rc = ipa_ws_reserve(ctx, (size_t)h * w);
     if (rc) return rc;
     unsigned char* g = (unsigned char*)ctx->ws;
-    hipLaunchKernelGGL(closest_rowdist_kernel, grid, block, 0, ctx->stream, d_arr, h, w, pitch, ksize,
-                       g);
-    if (out_dtype == IPA_U16)
-      hipLaunchKernelGGL((closest_coldist_kernel<unsigned short>), grid, block, 0, ctx->stream, d_arr,
-                         g, h, w, pitch, ksize, (unsigned short*)d_out, out_pitch);
-    else
-      hipLaunchKernelGGL((closest_coldist_kernel<double>), grid, block, 0, ctx->stream, d_arr, g, h, w,
-                         pitch, ksize, (double*)d_out, out_pitch);
-    IPA_HIP(ctx, hipGetLastError());
-    return IPA_OK;
+    rc = launch(ctx, closest_rowdist_kernel, grid, block, 0, d_arr, h, w, pitch, ksize, g);
+    if (rc) return rc;
+    return by_out([&](auto t) {
+      return launch(ctx, closest_coldist_kernel<decltype(t)>, grid, block, 0, d_arr, g, h, w, pitch,
+                    ksize, d_out, out_pitch);
+    });
   }
-  if (out_dtype == IPA_U16)
-    hipLaunchKernelGGL((closest_distance_kernel<unsigned short>), grid, block, 0, ctx->stream,
-                       d_arr, h, w, pitch, ksize, (unsigned short*)d_out, out_pitch);
-  else
-    hipLaunchKernelGGL((closest_distance_kernel<double>), grid, block, 0, ctx->stream, d_arr, h, w,
-                       pitch, ksize, (double*)d_out, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_out([&](auto t) {
+    return launch(ctx, closest_distance_kernel<decltype(t)>, grid, block, 0, d_arr, h, w, pitch,
+                  ksize, d_out, out_pitch);
+  });
 }
 
 int ipa_pos_intensity_unc_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
@@ -985,32 +963,14 @@ int ipa_pos_intensity_unc_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h,
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "pos_intensity_unc supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  {
-    const size_t lds = pos_intensity_unc_lds(ksize);
-    if (pos_intensity_unc_path(dtype, ksize) == 1) {
-      if (dtype == IPA_F32)
-        hipLaunchKernelGGL((pos_intensity_unc_sep_kernel<float>), grid, block, lds, ctx->stream,
-                           (const float*)d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize,
-                           d_sint, out_pitch);
-      else
-        hipLaunchKernelGGL((pos_intensity_unc_sep_kernel<double>), grid, block, lds, ctx->stream,
-                           (const double*)d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize,
-                           d_sint, out_pitch);
-      IPA_HIP(ctx, hipGetLastError());
-      return IPA_OK;
-    }
-  }
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL((pos_intensity_unc_kernel<float>), grid, block, 0, ctx->stream,
-                       (const float*)d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize,
-                       d_sint, out_pitch);
-  else
-    hipLaunchKernelGGL((pos_intensity_unc_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize,
-                       d_sint, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  const bool sep = pos_intensity_unc_path(dtype, ksize) == 1;
+  const size_t lds = sep ? pos_intensity_unc_lds(ksize) : 0;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(ctx, sep ? pos_intensity_unc_sep_kernel<T> : pos_intensity_unc_kernel<T>, grid,
+                  block, lds, d_img, h, w, pitch, d_sx, d_sy, sigma_pitch, sx, sy, ksize, d_sint,
+                  out_pitch);
+  });
 }
 
 int ipa_masked_mean_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsigned char* d_mask,
@@ -1024,39 +984,25 @@ int ipa_masked_mean_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsign
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "masked_mean supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-#define IPA_MM(T, FILL)                                                                          \
-  hipLaunchKernelGGL((masked_mean_kernel<T, FILL>), grid, block, 0, ctx->stream, (const T*)d_arr, \
-                     d_mask, h, w, pitch, mask_pitch, ksize / 2, (T*)d_out, out_pitch)
   if (fill_mask && d_out == d_arr) {
     // the in-place fill: wave-cooperative kernel (masked pixels are sparse)
     const int segs_x = (w + 63) / 64;
     const long segs = (long)segs_x * h;
     dim3 wgrid((unsigned)((segs + 3) / 4)), wblock(256);
     const bool cols = masked_mean_fill_path(dtype, ksize) == 1;
-    if (dtype == IPA_F32) {
-      if (cols)
-        hipLaunchKernelGGL((masked_mean_fill_cols_kernel<float>), wgrid, wblock, 0, ctx->stream,
-                           (float*)d_out, d_mask, h, w, pitch, mask_pitch, ksize / 2, segs_x);
-      else
-        hipLaunchKernelGGL((masked_mean_fill_wave_kernel<float>), wgrid, wblock, 0, ctx->stream,
-                           (float*)d_out, d_mask, h, w, pitch, mask_pitch, ksize / 2, segs_x);
-    } else {
-      if (cols)
-        hipLaunchKernelGGL((masked_mean_fill_cols_kernel<double>), wgrid, wblock, 0, ctx->stream,
-                           (double*)d_out, d_mask, h, w, pitch, mask_pitch, ksize / 2, segs_x);
-      else
-        hipLaunchKernelGGL((masked_mean_fill_wave_kernel<double>), wgrid, wblock, 0, ctx->stream,
-                           (double*)d_out, d_mask, h, w, pitch, mask_pitch, ksize / 2, segs_x);
-    }
-  } else if (dtype == IPA_F32) {
-    if (fill_mask) IPA_MM(float, true); else IPA_MM(float, false);
-  } else {
-    if (fill_mask) IPA_MM(double, true); else IPA_MM(double, false);
+    return by_float(dtype, [&](auto t) {
+      using T = decltype(t);
+      return launch(ctx, cols ? masked_mean_fill_cols_kernel<T> : masked_mean_fill_wave_kernel<T>,
+                    wgrid, wblock, 0, d_out, d_mask, h, w, pitch, mask_pitch, ksize / 2, segs_x);
+    });
   }
-#undef IPA_MM
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick<true, false>(fill_mask != 0, [&](auto FILL) {
+      return launch(ctx, masked_mean_kernel<T, FILL()>, grid, block, 0, d_arr, d_mask, h, w, pitch,
+                    mask_pitch, ksize / 2, d_out, out_pitch);
+    });
+  });
 }
 
 int ipa_masked_median_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsigned char* d_mask,
@@ -1077,19 +1023,13 @@ int ipa_masked_median_dev(ipa_ctx* ctx, const void* d_arr, int dtype, const unsi
   const int segs_x = (w + 63) / 64;
   const long segs = (long)segs_x * h;
   dim3 grid((unsigned)((segs + 3) / 4)), block(256);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-#define IPA_MMED(T, FILL)                                                                       \
-  hipLaunchKernelGGL((masked_median_wave_kernel<T, FILL>), grid, block, lds, ctx->stream,       \
-                     (const T*)d_arr, d_mask, h, w, pitch, mask_pitch, k, cap, segs_x, (T*)d_out, \
-                     out_pitch)
-  if (dtype == IPA_F32) {
-    if (fill_mask) IPA_MMED(float, true); else IPA_MMED(float, false);
-  } else {
-    if (fill_mask) IPA_MMED(double, true); else IPA_MMED(double, false);
-  }
-#undef IPA_MMED
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick<true, false>(fill_mask != 0, [&](auto FILL) {
+      return launch(ctx, masked_median_wave_kernel<T, FILL()>, grid, block, lds, d_arr, d_mask, h,
+                    w, pitch, mask_pitch, k, cap, segs_x, d_out, out_pitch);
+    });
+  });
 }
 
 int ipa_nan_max_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, int w, long pitch,
@@ -1101,31 +1041,20 @@ int ipa_nan_max_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, int w, lo
   IPA_REQUIRE(ctx, d_arr != d_out, "nan_max cannot run in place");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "nan_max supports float32/float64 (got dtype %d)", dtype);
-  dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  {
-    const int k = ksize / 2, rb = kNanMaxRB;
+  const int k = ksize / 2, rb = kNanMaxRB;
+  if (nan_max_path(dtype, ksize) == 1) {
     const size_t lds = nan_max_sep_lds(dtype, ksize);
-    if (nan_max_path(dtype, ksize) == 1) {
-      dim3 sgrid((w + 63) / 64, (h + rb - 1) / rb), sblock(256);
-      if (dtype == IPA_F32)
-        hipLaunchKernelGGL((nan_max_sep_kernel<float>), sgrid, sblock, lds, ctx->stream,
-                           (const float*)d_arr, h, w, pitch, k, rb, (float*)d_out, out_pitch);
-      else
-        hipLaunchKernelGGL((nan_max_sep_kernel<double>), sgrid, sblock, lds, ctx->stream,
-                           (const double*)d_arr, h, w, pitch, k, rb, (double*)d_out, out_pitch);
-      IPA_HIP(ctx, hipGetLastError());
-      return IPA_OK;
-    }
+    dim3 sgrid((w + 63) / 64, (h + rb - 1) / rb), sblock(256);
+    return by_float(dtype, [&](auto t) {
+      return launch(ctx, nan_max_sep_kernel<decltype(t)>, sgrid, sblock, lds, d_arr, h, w, pitch, k,
+                    rb, d_out, out_pitch);
+    });
   }
-  if (dtype == IPA_F32)
-    hipLaunchKernelGGL((nan_max_kernel<float>), grid, block, 0, ctx->stream, (const float*)d_arr,
-                       h, w, pitch, ksize / 2, (float*)d_out, out_pitch);
-  else
-    hipLaunchKernelGGL((nan_max_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_arr, h, w, pitch, ksize / 2, (double*)d_out, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
+  return by_float(dtype, [&](auto t) {
+    return launch(ctx, nan_max_kernel<decltype(t)>, grid, block, 0, d_arr, h, w, pitch, k, d_out,
+                  out_pitch);
+  });
 }
 
 int ipa_conv_ydep_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, long src_pitch,
@@ -1142,27 +1071,13 @@ int ipa_conv_ydep_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "conv_ydep supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t lds = conv_ydep_tile_lds(dtype, k0, k1);
-  if (conv_ydep_path(dtype, k0, k1) == 1) {  // the window of a block fits in LDS: staged version
-    if (dtype == IPA_F32)
-      hipLaunchKernelGGL((conv_ydep_tile_kernel<float>), grid, block, lds, ctx->stream,
-                         (const float*)d_src, h, w, src_pitch, d_kernels, k0, k1, border_x,
-                         border_y, (float*)d_dst, dst_pitch);
-    else
-      hipLaunchKernelGGL((conv_ydep_tile_kernel<double>), grid, block, lds, ctx->stream,
-                         (const double*)d_src, h, w, src_pitch, d_kernels, k0, k1, border_x,
-                         border_y, (double*)d_dst, dst_pitch);
-  } else if (dtype == IPA_F32)
-    hipLaunchKernelGGL((conv_ydep_kernel<float>), grid, block, 0, ctx->stream, (const float*)d_src,
-                       h, w, src_pitch, d_kernels, k0, k1, border_x, border_y, (float*)d_dst,
-                       dst_pitch);
-  else
-    hipLaunchKernelGGL((conv_ydep_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_src, h, w, src_pitch, d_kernels, k0, k1, border_x,
-                       border_y, (double*)d_dst, dst_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  const bool tile = conv_ydep_path(dtype, k0, k1) == 1;  // the window of a block fits in LDS: staged version
+  const size_t lds = tile ? conv_ydep_tile_lds(dtype, k0, k1) : 0;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(ctx, tile ? conv_ydep_tile_kernel<T> : conv_ydep_kernel<T>, grid, block, lds,
+                  d_src, h, w, src_pitch, d_kernels, k0, k1, border_x, border_y, d_dst, dst_pitch);
+  });
 }
 
 int ipa_local_std_dev(ipa_ctx* ctx, const void* d_img, const void* d_blurred, int dtype, int h,
@@ -1175,37 +1090,23 @@ int ipa_local_std_dev(ipa_ctx* ctx, const void* d_img, const void* d_blurred, in
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "local_std supports float32/float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
   const int hkx = ksize_x / 2, hky = ksize_y / 2;
   const int path = local_std_path(dtype, ksize_x, ksize_y);
   // square windows up to 11: 256-px tiles, 4 pixels per lane (stencils_ydep.hip)
   if (path == 1) {
-    if (ipa_local_std_wave_launch(ctx, d_img, d_blurred, dtype, h, w, pitch, blurred_pitch, hkx,
-                                  hky, d_out, out_pitch) != 0)
+    const int rc = ipa_local_std_wave_launch(ctx, d_img, d_blurred, dtype, h, w, pitch,
+                                             blurred_pitch, hkx, hky, d_out, out_pitch);
+    if (rc == kNotCovered)
       IPA_UNSUPPORTED(ctx, "local_std: no wave kernel for half window %d", hkx);
-    IPA_HIP(ctx, hipGetLastError());
-    return IPA_OK;
+    return rc;
   }
-  const size_t lds = local_std_tile_lds(dtype, hkx, hky);
-  if (path == 2) {  // the block's window fits in LDS: staged version
-    if (dtype == IPA_F32)
-      hipLaunchKernelGGL((local_std_tile_kernel<float>), grid, block, lds, ctx->stream,
-                         (const float*)d_img, (const float*)d_blurred, h, w, pitch, blurred_pitch,
-                         hkx, hky, (float*)d_out, out_pitch);
-    else
-      hipLaunchKernelGGL((local_std_tile_kernel<double>), grid, block, lds, ctx->stream,
-                         (const double*)d_img, (const double*)d_blurred, h, w, pitch,
-                         blurred_pitch, hkx, hky, (double*)d_out, out_pitch);
-  } else if (dtype == IPA_F32)
-    hipLaunchKernelGGL((local_std_kernel<float>), grid, block, 0, ctx->stream, (const float*)d_img,
-                       (const float*)d_blurred, h, w, pitch, blurred_pitch, ksize_x / 2,
-                       ksize_y / 2, (float*)d_out, out_pitch);
-  else
-    hipLaunchKernelGGL((local_std_kernel<double>), grid, block, 0, ctx->stream,
-                       (const double*)d_img, (const double*)d_blurred, h, w, pitch, blurred_pitch,
-                       ksize_x / 2, ksize_y / 2, (double*)d_out, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  const bool tile = path == 2;  // the block's window fits in LDS: staged version
+  const size_t lds = tile ? local_std_tile_lds(dtype, hkx, hky) : 0;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return launch(ctx, tile ? local_std_tile_kernel<T> : local_std_kernel<T>, grid, block, lds,
+                  d_img, d_blurred, h, w, pitch, blurred_pitch, hkx, hky, d_out, out_pitch);
+  });
 }
 
 // which kernel an entry point above (and ipa_var_y_gauss_dev) launches: stencil_paths.hpp

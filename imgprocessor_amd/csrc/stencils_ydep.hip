@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "stencil_paths.hpp"
 
 namespace ipa {
@@ -277,36 +278,26 @@ local_std_wave_kernel(const T* __restrict__ img, const T* __restrict__ blurred, 
   }
 }
 
-template <typename T, int HK>
-static void local_std_wave_launch(ipa_ctx* ctx, const void* img, const void* blurred, int h, int w,
-                                  long pitch, long bpitch, void* out, long opitch) {
-  // rows per block, 4K float32 frame: 4: 45.7 us, 8: 41.7, 12: 41.5, 16: 44.8, 24: 54.0, 32: 49.8
-  const int rb = sizeof(T) == 4 ? 12 : 16;
-  const size_t lds = (size_t)(rb + 2 * HK) * (kYdepTW + 2 * HK + 3) * sizeof(T);
-  const int vec_out = (((uintptr_t)out) % 16 == 0) && ((opitch * (long)sizeof(T)) % 16 == 0);
-  dim3 grid((w + kYdepTW - 1) / kYdepTW, (h + rb - 1) / rb), block(256);
-  hipLaunchKernelGGL((local_std_wave_kernel<T, HK>), grid, block, lds, ctx->stream, (const T*)img,
-                     (const T*)blurred, h, w, pitch, bpitch, rb, (T*)out, opitch, vec_out);
-}
-
 }  // namespace ipa
 
 using namespace ipa;
 
-// the square windows of local_std_path() == 1 (hk = 1..5)
+// the square windows of local_std_path() == 1 (hk = 1..5); contract: launch.hpp
 int ipa_local_std_wave_launch(ipa_ctx* ctx, const void* img, const void* blurred, int dtype, int h,
                               int w, long pitch, long bpitch, int hkx, int hky, void* out,
                               long opitch) {
-#define IPA_STD_CASE(HK)                                                                          \
-  case HK:                                                                                        \
-    if (dtype == IPA_F32) local_std_wave_launch<float, HK>(ctx, img, blurred, h, w, pitch, bpitch, out, opitch); \
-    else local_std_wave_launch<double, HK>(ctx, img, blurred, h, w, pitch, bpitch, out, opitch);  \
-    return 0;
-  switch (hkx) {
-    IPA_STD_CASE(1) IPA_STD_CASE(2) IPA_STD_CASE(3) IPA_STD_CASE(4) IPA_STD_CASE(5)
-  }
-#undef IPA_STD_CASE
-  return 1;
+  return by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    // rows per block, 4K float32 frame: 4: 45.7 us, 8: 41.7, 12: 41.5, 16: 44.8, 24: 54.0, 32: 49.8
+    const int rb = sizeof(T) == 4 ? 12 : 16;
+    const int vec_out = (((uintptr_t)out) % 16 == 0) && ((opitch * (long)sizeof(T)) % 16 == 0);
+    dim3 grid((w + kYdepTW - 1) / kYdepTW, (h + rb - 1) / rb), block(256);
+    return pick<1, 2, 3, 4, 5>(hkx, [&](auto HK) {
+      const size_t lds = (size_t)(rb + 2 * HK()) * (kYdepTW + 2 * HK() + 3) * sizeof(T);
+      return launch(ctx, local_std_wave_kernel<T, HK()>, grid, block, lds, img, blurred, h, w,
+                    pitch, bpitch, rb, out, opitch, vec_out);
+    });
+  });
 }
 
 extern "C" {
@@ -345,13 +336,14 @@ int ipa_var_y_gauss_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w
   IPA_HIP(ctx, hipMemcpyAsync(d_rowk, rowk, (size_t)kx * sizeof(double), hipMemcpyHostToDevice,
                               ctx->stream));
   // rowk is caller memory: the copy above must have read it before we return
-  hipLaunchKernelGGL(ydep_gauss_cols_kernel, dim3((h * ky + 255) / 256), dim3(256), 0, ctx->stream,
-                     h, ky, sig_min, sig_max, 4.0, d_cols);
+  rc = launch(ctx, ydep_gauss_cols_kernel, dim3((h * ky + 255) / 256), dim3(256), 0, h, ky, sig_min,
+              sig_max, 4.0, d_cols);
+  if (rc) return rc;
   if (!tiled) {
     const long n = (long)h * ky * kx;
-    hipLaunchKernelGGL(ydep_outer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       ctx->stream, d_cols, d_rowk, (long)h * ky, kx, d_table);
-    IPA_HIP(ctx, hipGetLastError());
+    rc = launch(ctx, ydep_outer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_cols,
+                d_rowk, (long)h * ky, kx, d_table);
+    if (rc) return rc;
     rc = ipa_conv_ydep_dev(ctx, d_src, dtype, h, w, src_pitch, d_table, ky, kx, border_x,
                            border_y, d_dst, dst_pitch);
     if (rc) return rc;
@@ -360,23 +352,15 @@ int ipa_var_y_gauss_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w
   }
   const int vec_out = (((uintptr_t)d_dst) % 16 == 0) && ((dst_pitch * (long)esz) % 16 == 0);
   dim3 grid((w + kYdepTW - 1) / kYdepTW, (h + rb - 1) / rb), block(256);
-#define IPA_YDEP_LAUNCH(T, K1)                                                                 \
-  hipLaunchKernelGGL((conv_ydep_sep_kernel<T, K1>), grid, block, plan.lds, ctx->stream,           \
-                     (const T*)d_src, h, w, src_pitch, d_cols, ky, d_rowk, kx, border_x, border_y, \
-                     rb, (T*)d_dst, dst_pitch, vec_out)
-  if (dtype == IPA_F32) {
-    if (kx == 1) IPA_YDEP_LAUNCH(float, 1);
-    else if (kx == 3) IPA_YDEP_LAUNCH(float, 3);
-    else if (kx == 5) IPA_YDEP_LAUNCH(float, 5);
-    else IPA_YDEP_LAUNCH(float, 0);
-  } else {
-    if (kx == 1) IPA_YDEP_LAUNCH(double, 1);
-    else if (kx == 3) IPA_YDEP_LAUNCH(double, 3);
-    else if (kx == 5) IPA_YDEP_LAUNCH(double, 5);
-    else IPA_YDEP_LAUNCH(double, 0);
-  }
-#undef IPA_YDEP_LAUNCH
-  IPA_HIP(ctx, hipGetLastError());
+  rc = by_float(dtype, [&](auto t) {
+    using T = decltype(t);
+    return pick_or_last<1, 3, 5, 0>(kx, [&](auto K1) {
+      return launch(ctx, conv_ydep_sep_kernel<T, K1()>, grid, block, plan.lds, d_src, h, w,
+                    src_pitch, d_cols, ky, d_rowk, kx, border_x, border_y, rb, d_dst, dst_pitch,
+                    vec_out);
+    });
+  });
+  if (rc) return rc;
   IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // rowk (host) may be reused by the caller
   return IPA_OK;
 }

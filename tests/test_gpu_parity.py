@@ -695,6 +695,31 @@ def test_idw_edges_vs_oracle(ia, oracle):
                      oracle.interpolate2dStructuredFastIDW(grid.copy(), mask, k, 2, 5), 1e-12, 1e-14)
 
 
+def test_idw_kernel_boundaries_vs_oracle(ia, oracle):
+    """Both IDW kernels in both types: a window of 2 k + 1 = 17 ... 64 columns runs with the lanes
+    over the columns of a window row, any other with the lanes over the taps (idw_path,
+    stencil_paths.hpp) - k = 7 | 8 and 31 | 32 stand on either side of both ends.  And the fast
+    IDW in float32, which nothing else runs."""
+    from imgprocessor_amd.interpolate import (interpolate2dStructuredIDW,
+                                               interpolate2dStructuredFastIDW)
+    rng = np.random.default_rng(9)
+    for (H, W) in ((40, 150), (65, 64)):
+        grid = rng.random((H, W))
+        mask = rng.random((H, W)) < 0.3  # masked pixels right up to every edge
+        g32 = grid.astype(np.float32)
+        for k in (7, 8, 31, 32):
+            what = 'idw %dx%d k%d' % (H, W, k)
+            assert_close(interpolate2dStructuredIDW(grid.copy(), mask, k, 2),
+                         oracle.interpolate2dStructuredIDW(grid.copy(), mask, k, 2), 1e-12, 1e-14, what)
+            close32(interpolate2dStructuredIDW(g32.copy(), mask, k, 2),
+                    oracle.interpolate2dStructuredIDW(g32.copy(), mask, k, 2), what + ' f32')
+        what = 'fast idw %dx%d' % (H, W)
+        assert_close(interpolate2dStructuredFastIDW(grid.copy(), mask, 4, 2, 5),
+                     oracle.interpolate2dStructuredFastIDW(grid.copy(), mask, 4, 2, 5), 1e-12, 1e-14, what)
+        close32(interpolate2dStructuredFastIDW(g32.copy(), mask, 4, 2, 5),
+                oracle.interpolate2dStructuredFastIDW(g32.copy(), mask, 4, 2, 5), what + ' f32')
+
+
 # ------------------------------------------------------- drop-in surface ----
 def test_lens_distortion_class(ia, oracle):
     from imgprocessor_amd.camera.LensDistortion import LensDistortion
