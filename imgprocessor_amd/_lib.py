@@ -21,6 +21,9 @@ BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT10
  STENCIL_CLOSEST_DISTANCE, STENCIL_POS_INTENSITY_UNC, STENCIL_MEDIAN_THRESHOLD,
  STENCIL_VAR_Y_GAUSS, STENCIL_CONV_YDEP) = range(9)
 
+# ipa_conv_op of ipa_conv_path
+CONV_CONV2D, CONV_SEPCONV2D, CONV_SEPCONV2D_LDS = range(3)
+
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t
@@ -82,6 +85,7 @@ PROTOTYPES = {
     'ipa_median_threshold_dev': [_vp, _vp, _i, _i, _i, _l, _d, _i, _vp, _l, _vp, _l],
     'ipa_median_threshold_size_dev': [_vp, _vp, _i, _i, _i, _l, _i, _d, _i, _vp, _l, _vp, _l],
     'ipa_stencil_path': [_i, _i, _i, _i],
+    'ipa_conv_path': [_i, _i, _i, _i, _i],
     'ipa_calib_prefilter_dev': [_vp, _vp, _i, _vp, _vp, _i, _i, _l, _l, _l, _d, _vp, _l],
     'ipa_remap_conv2d_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _dp, _i, _i, _vp, _i, _i,
                              _i, _l, _i, _l, _l, _i, _i, _d, _i, _i],

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "conv_paths.hpp"
 #include "conv_tile.hpp"
 #include "wave_stencil.hpp"
 
@@ -176,8 +177,7 @@ conv_generic_kernel(ConvParams p, const T* __restrict__ wts, int kh, int kw) {
 }
 
 // ------------------------------------------------------------- separable --
-constexpr int kSepMaxTaps = 63;
-
+// (kSepMaxTaps = 63 taps per axis: conv_paths.hpp)
 template <typename T> struct SepWeights {
   T ky[kSepMaxTaps];
   T kx[kSepMaxTaps];
@@ -360,14 +360,14 @@ static void launch_conv(ipa_ctx* ctx, const ConvParams& p, const double* kernel,
 template <typename T>
 static int conv_typed(ipa_ctx* ctx, ConvParams& p, const double* kernel, int kh, int kw,
                       int n_frames) {
-  bool fast = (kh == kw) && (kh == 3 || kh == 5 || kh == 7 || kh == 9 || kh == 11);
-  if (fast && sizeof(T) == 8 && kh > 7) fast = false;  // f64: tuned path instantiated to 7x7
+  // wave / LDS tile / generic: conv2d_path (conv_paths.hpp)
+  const int path = conv2d_path(sizeof(T) == 4 ? IPA_F32 : IPA_F64, kh, kw, p.mask != nullptr,
+                               ctx->tune.big_wave != 0);
   if constexpr (sizeof(T) == 4) {
     // float32: the wave-marching stencil (wave_stencil.hpp)
     // (masked filtering stays on the LDS-tiled kernel; so do 9x9 / 11x11 with the context knob big_wave = 0,
     // the tuning knob that A/Bs wave_conv_big.hip against it: 334 vs 375 us, 428 vs 487 us)
-    const bool big_wave = ctx->tune.big_wave != 0;
-    if (fast && (kh <= 7 || big_wave) && !p.mask) {
+    if (path == kConvWave) {
       WaveParams wp;
       wp.dst = p.dst; wp.dst_frame_elems = p.dst_frame_elems;
       wp.dh = p.h; wp.dw = p.w; wp.dpitch = p.dpitch;
@@ -388,7 +388,7 @@ static int conv_typed(ipa_ctx* ctx, ConvParams& p, const double* kernel, int kh,
       return IPA_OK;
     }
   }
-  if (fast) {
+  if (path == kConvTile) {
     switch (kh) {
       case 3: launch_conv<T, 3>(ctx, p, kernel, n_frames); break;
       case 5: launch_conv<T, 5>(ctx, p, kernel, n_frames); break;
@@ -404,7 +404,7 @@ static int conv_typed(ipa_ctx* ctx, ConvParams& p, const double* kernel, int kh,
     return IPA_OK;
   }
   // generic: weights through the table arena
-  IPA_REQUIRE(ctx, (long)kh * kw <= 65536, "kernel too large (%dx%d)", kh, kw);
+  IPA_REQUIRE(ctx, (long)kh * kw <= kConvGenericMaxTaps, "kernel too large (%dx%d)", kh, kw);
   IPA_REQUIRE(ctx, n_frames <= 65535, "n_frames too large");
   std::vector<T> hw((size_t)kh * kw);
   for (size_t i = 0; i < hw.size(); i++) hw[i] = (T)kernel[i];
@@ -529,11 +529,9 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
     // long kernels (e.g. sigma = 11 -> 89 taps, filters/standardDeviation.py:23) do not fit
     // the kernarg table / LDS planes: run the two axes as two launches of the generic
     // correlation with the intermediate (rounded to the image dtype, like scipy) in a
-    // temporary device buffer
+    // temporary device buffer (sepconv_long, conv_paths.hpp)
     size_t es0 = ipa_dtype_size(dtype);
-    int hxa0 = ((nkx / 2 + 3) / 4) * 4;
-    size_t lds0 = (size_t)(2 * kTileH + 2 * (nky / 2)) * (kTileW + 2 * hxa0) * es0;
-    if (nky > kSepMaxTaps || nkx > kSepMaxTaps || lds0 > 150 * 1024) {
+    if (sepconv_long(es0, nky, nkx)) {
       IPA_REQUIRE(ctx, d_src != d_dst, "sepconv2d cannot run in place");
       if (nky == 0 || nkx == 0) {
         const double* k = nky ? ky : kx;
@@ -567,7 +565,7 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "sepconv2d supports float32/float64 images (got dtype %d)", dtype);
   size_t es = ipa_dtype_size(dtype);
-  if (dtype == IPA_F32 && nky == nkx && (nky == 3 || nky == 5 || nky == 7 || nky == 9)) {
+  if (sepconv_wave(dtype, nky, nkx)) {
     // float32, equal short tap counts: the wave-marching separable kernel (wave_sep.hip)
     WaveParams wp;
     wp.dst = (char*)d_dst; wp.dst_frame_elems = dst_frame_stride;
@@ -595,8 +593,7 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   p.hxa = ((p.hx + 3) / 4) * 4;
   p.vec_in = rows_aligned16(d_src, src_pitch, src_frame_stride, n_frames, es);
   p.vec_out = rows_aligned16(d_dst, dst_pitch, dst_frame_stride, n_frames, es);
-  int LW = kTileW + 2 * p.hxa;
-  size_t lds = (size_t)(kTileH + 2 * p.hy + kTileH) * LW * es;
+  size_t lds = sepconv_lds(es, nky, nkx);
   IPA_REQUIRE(ctx, lds <= 160 * 1024, "separable kernel too large for LDS");
   dim3 grid(p.tiles, (unsigned)n_frames), block(32, 8);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
@@ -604,7 +601,7 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
     SepWeights<float> sw;
     for (int i = 0; i < nky; i++) sw.ky[i] = (float)ky[i];
     for (int i = 0; i < nkx; i++) sw.kx[i] = (float)kx[i];
-    if (lds > 64 * 1024)
+    if (lds > kSepLdsOptIn)
       IPA_HIP(ctx, hipFuncSetAttribute((const void*)sepconv_kernel<float>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((sepconv_kernel<float>), grid, block, lds, ctx->stream, p, sw);
@@ -612,7 +609,7 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
     SepWeights<double> sw;
     for (int i = 0; i < nky; i++) sw.ky[i] = ky[i];
     for (int i = 0; i < nkx; i++) sw.kx[i] = kx[i];
-    if (lds > 64 * 1024)
+    if (lds > kSepLdsOptIn)
       IPA_HIP(ctx, hipFuncSetAttribute((const void*)sepconv_kernel<double>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((sepconv_kernel<double>), grid, block, lds, ctx->stream, p, sw);
@@ -668,6 +665,20 @@ int ipa_deinterleave_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int 
 int ipa_interleave_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, int channels,
                        long src_pitch, long src_plane_stride, void* d_dst, long dst_pitch) {
   return channels_launch<false>(ctx, d_src, dtype, h, w, channels, dst_pitch, src_pitch, src_plane_stride, d_dst);
+}
+
+// which kernel the two entry points above launch: conv_paths.hpp
+int ipa_conv_path(int op, int dtype, int k0, int k1, int flags) {
+  switch (op) {
+    case IPA_CONV_CONV2D: return conv2d_path(dtype, k0, k1, (flags & 1) != 0, (flags & 2) == 0);
+    case IPA_CONV_SEPCONV2D: return sepconv2d_path(dtype, k0, k1);
+    case IPA_CONV_SEPCONV2D_LDS: {
+      if (!conv_float(dtype) || k0 < 0 || k1 < 0) return 0;
+      const size_t lds = sepconv_lds(ipa_dtype_size(dtype), k0, k1);
+      return lds > 0x7fffffff ? 0x7fffffff : (int)lds;
+    }
+  }
+  return -1;
 }
 
 // ---------------------------------------------------- host-pointer variants --

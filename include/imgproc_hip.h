@@ -206,7 +206,13 @@ int ipa_conv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const dou
  * ky[nky] first, intermediate rounded to the image dtype, then axis 1 (x) with
  * kx[nkx].  nky==0 / nkx==0 skips that axis.  Replaces the gaussian_filter call
  * sites filters/standardDeviation.py:23, filters/fastFilter.py:42,
- * camera/flatField/flatField.py:47.  Single pass over HBM. */
+ * camera/flatField/flatField.py:47.  Single pass over HBM.
+ * Tap counts: up to 63 per axis (and two LDS planes within 150 KiB) run in the single-pass
+ * kernels, which are centred on an odd count only - an EVEN count there is IPA_ERR_BAD_ARG.
+ * Longer kernels run axis by axis on the generic correlation BEFORE that check, so an even
+ * count of 64 taps or more is accepted and centred on tap n / 2 like scipy's correlate1d
+ * (tests/test_gpu_conv_paths.py pins both).  The inconsistency is known and kept: callers that
+ * need even kernels of any length have ipa_conv2d_dev with kh or kw = 1. */
 int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, long src_pitch,
                       const double* ky, int nky, const double* kx, int nkx, void* d_dst,
                       long dst_pitch, int n_frames, long src_frame_stride, long dst_frame_stride,
@@ -214,6 +220,25 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
 int ipa_sepconv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const double* ky,
                   int nky, const double* kx, int nkx, void* dst, int n_frames, int border_y,
                   int border_x, double border_value);
+
+/* Which kernel ipa_conv2d_dev / ipa_sepconv2d_dev launch for a kernel shape and dtype: the
+ * launchers' own selection arithmetic (csrc/conv_paths.hpp), without a context or a device.
+ * Returns 0 = refused, 1.. = the kernels in the order listed, -1 = unknown op.  The rank-1
+ * routing of a dense float32 9x9 (knob rank1_sep, counter rank1_routed) depends on the kernel's
+ * values and happens before this selection: it is not part of the query. */
+typedef enum {
+  IPA_CONV_CONV2D = 0,       /* k0, k1 = kh, kw; flags bit 0: with a mask, bit 1: knob big_wave
+                                == 0.  1 marching wave (float32, no mask, square 3/5/7, and
+                                9/11 unless big_wave == 0), 2 LDS tile (float32 square 3..11
+                                otherwise, float64 square 3/5/7), 3 generic */
+  IPA_CONV_SEPCONV2D = 1,    /* k0, k1 = nky, nkx.  1 marching separable wave (float32,
+                                nky == nkx in 3/5/7/9), 2 LDS kernel within 64 KiB, 3 LDS kernel
+                                with the dynamic-LDS opt-in, 4 two generic launches through a
+                                temporary, 5 one generic launch (long kernel on one axis only) */
+  IPA_CONV_SEPCONV2D_LDS = 2 /* k0, k1 = nky, nkx: not a path but the bytes of dynamic LDS the
+                                LDS kernel needs (the formula behind 2 / 3 / 4 above) */
+} ipa_conv_op;
+int ipa_conv_path(int op, int dtype, int k0, int k1, int flags);
 
 /* replaces filters/varYSizeGaussianFilter.py:53-68 (_2dConvolutionYdependentKernel):
  *   dst[r,c] = sum_{ii<k0, jj<k1} kernels[r][ii][jj] * src[r+ii-k0/2, c+jj-k1/2]

@@ -299,8 +299,6 @@ def test_conv2d_shapes_and_masks(ia, oracle):
     for (H, W) in ((1, 1), (3, 5), (31, 33), (32, 128), (33, 129), (130, 70)):
         img = rng.random((H, W)).astype(np.float32)
         for K in (3, 5):
-            if K // 2 >= min(H, W) and (H, W) != (1, 1):
-                continue
             k = rng.random((K, K))
             got = ia.ops.conv2d(img, k, 'reflect')
             close32(got, oracle.conv2d(img, k, 'reflect'), 'shape %s k%d' % ((H, W), K))
