@@ -24,6 +24,13 @@ BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT10
 # ipa_conv_op of ipa_conv_path
 CONV_CONV2D, CONV_SEPCONV2D, CONV_SEPCONV2D_LDS = range(3)
 
+# ipa_interp_op / ipa_interp_const of ipa_interp_path
+(INTERP_CONST, INTERP_CROSS_FASTDIV, INTERP_CIRCULAR_FASTDIV, INTERP_FASTDIV_MUL, INTERP_POWER,
+ INTERP_POINT_SPREAD_ROWS, INTERP_STAT_SAMPLES, INTERP_RESIZE_VEC4, INTERP_RESIZE_AREA,
+ INTERP_RESIZE_LINEAR) = range(10)
+(INTERP_K_CROSS_SEG, INTERP_K_CROSS_BALLOT_STEPS, INTERP_K_CROSS_SEARCH_PASS,
+ INTERP_K_FASTDIV_SHIFT, INTERP_K_PS_WAVES, INTERP_K_PS_MAX_ROWS, INTERP_K_STAT_MAX) = range(7)
+
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t
@@ -86,6 +93,7 @@ PROTOTYPES = {
     'ipa_median_threshold_size_dev': [_vp, _vp, _i, _i, _i, _l, _i, _d, _i, _vp, _l, _vp, _l],
     'ipa_stencil_path': [_i, _i, _i, _i],
     'ipa_conv_path': [_i, _i, _i, _i, _i],
+    'ipa_interp_path': [_i, _d, _d, _d, _d],
     'ipa_calib_prefilter_dev': [_vp, _vp, _i, _vp, _vp, _i, _i, _l, _l, _l, _d, _vp, _l],
     'ipa_remap_conv2d_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _dp, _i, _i, _vp, _i, _i,
                              _i, _l, _i, _l, _l, _i, _i, _d, _i, _i],

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "interp_paths.hpp"
 #include "launch.hpp"
 
 // the reference's float64 expressions operation for operation: no fused multiply-add (hipcc
@@ -107,11 +108,11 @@ circular_idw_kernel(T* __restrict__ grid, const uint8_t* __restrict__ mask, int 
     const double di = (double)row - cx, dj = (double)j - cy;
     const double R = sqrt(di * di + dj * dj), PHI = atan2(dj, di);
     double sw = 0.0, sv = 0.0;
-    // (t / ny by a multiplication, exact while t ny < 2^20 - see cross_local_avg_kernel)
-    const bool fastdiv = ny > 0 && (long)nx * ny * ny < (1l << 20);
-    const unsigned M = ny > 0 ? ((1u << 20) + (unsigned)ny - 1u) / (unsigned)ny : 0u;
+    // (t / ny by a multiplication, exact while t ny < 2^20 - interp_paths.hpp)
+    const bool fastdiv = circular_fastdiv(nx, ny);
+    const unsigned M = ny > 0 ? fastdiv_mul(ny) : 0u;
     for (int t = lane; t < nx * ny; t += 64) {
-      const int a = fastdiv ? (int)(((unsigned long long)(unsigned)t * M) >> 20) : t / ny;
+      const int a = fastdiv ? (int)(((unsigned long long)(unsigned)t * M) >> kFastDivShift) : t / ny;
       const int xi = xmn + a, yi = ymn + (t - a * ny);
       // (mask, table entry and value loaded side by side: one round trip per pass)
       const uint8_t mk = mask[(long)xi * w + yi];
@@ -136,13 +137,7 @@ circular_idw_kernel(T* __restrict__ grid, const uint8_t* __restrict__ mask, int 
 }
 
 // ---------------------------------------------------------------- cross average --
-// pixels of a row one wave looks after: the wave works through ITS masked pixels one after the
-// other, so a hole costs the launch the time of the wave with the most hole pixels (4K with a
-// 200 x 400 hole + 2 % scattered, kernel 5: 64 per wave 906 us, 16 per wave 852)
-#ifndef IPA_CROSS_SEG
-#define IPA_CROSS_SEG 16
-#endif
-constexpr int kCrossSeg = IPA_CROSS_SEG;
+// (kCrossSeg pixels of a row per wave: interp_paths.hpp)
 // Pass 1: _localAvg (:21-44) at every unmasked pixel that can be the end of a search - one with
 // a masked 4-neighbour - stored in the grid's dtype (the reference's `vals` array).
 template <typename T>
@@ -174,13 +169,13 @@ cross_local_avg_kernel(const T* __restrict__ grid, const uint8_t* __restrict__ m
     double sv = 0.0, sn = 0.0;
     // t / ny by a multiplication while t * ny < 2^20 (exact there: M = ceil(2^20 / ny) errs by
     // less than one part in 2^20 / ny) - the integer division was a third of the loop
-    const bool fastdiv = (long)nt * ny < (1l << 20);
-    const unsigned M = ((1u << 20) + (unsigned)ny - 1u) / (unsigned)ny;
+    const bool fastdiv = cross_fastdiv(nt, ny);
+    const unsigned M = fastdiv_mul(ny);
     // two positions per pass, mask and value loaded side by side (the value of a masked
     // position is dropped): one memory round trip per 128 positions instead of two per 64 - the
     // loop waits for its loads and nothing else.  Per-lane order of the sums unchanged.
     auto at = [&](int t, long& mi, long& gi) {
-      const int a = fastdiv ? (int)(((unsigned long long)(unsigned)t * M) >> 20) : t / ny;
+      const int a = fastdiv ? (int)(((unsigned long long)(unsigned)t * M) >> kFastDivShift) : t / ny;
       const int xi = xmn + a, yi = ymn + (t - a * ny);
       mi = (long)xi * w + yi;
       gi = (long)xi * pitch + yi;
@@ -252,7 +247,8 @@ cross_prev_row_kernel(const int* __restrict__ rowlast, int h, int* __restrict__ 
 // `count` steps, 0 when there is none: 64 positions per pass
 __device__ __forceinline__ int cross_search(const uint8_t* __restrict__ mask, int w, int row,
                                             int col, int dr, int dc, int count, int lane) {
-  for (int c = 0; c < count; c += 64) {
+  static_assert(kCrossSearchPass == 64, "one step per lane of a wave");
+  for (int c = 0; c < count; c += kCrossSearchPass) {
     const int t = c + lane + 1;
     const bool un = t <= count && mask[(long)(row + t * dr) * w + (col + t * dc)] == 0;
     const unsigned long long hit = __ballot(un);
@@ -287,6 +283,7 @@ cross_fill_kernel(T* __restrict__ grid, const uint8_t* __restrict__ mask, int h,
     // isolated masked pixel ends every search there - one memory round trip instead of four
     // (4K, 2 % scattered + a 200 x 400 hole, kernel 5: 615 -> 566 us for the whole fill)
     const int c0 = row, c1 = h - 1 - row, c2n = j, c3 = row < w - 1 ? w - 1 - j : 0;
+    static_assert(kCrossBallotSteps == 8, "lanes 8 d .. 8 d + 7 hold direction d");
     const int dir = lane >> 3, t = (lane & 7) + 1;
     const int cnt = dir == 0 ? c0 : (dir == 1 ? c1 : (dir == 2 ? c2n : c3));
     const int pr = row + (dir == 0 ? -t : (dir == 1 ? t : 0)), pc = j + (dir == 2 ? -t : (dir == 3 ? t : 0));
@@ -294,7 +291,7 @@ cross_fill_kernel(T* __restrict__ grid, const uint8_t* __restrict__ mask, int h,
     auto near = [&](int d, int count, int dr, int dc) {
       const unsigned hd = (unsigned)(hit8 >> (8 * d)) & 0xffu;
       if (hd) return (int)__ffs((int)hd);
-      return count > 8 ? cross_search(mask, w, row, j, dr, dc, count, lane) : 0;
+      return count > kCrossBallotSteps ? cross_search(mask, w, row, j, dr, dc, count, lane) : 0;
     };
     const int d0 = near(0, c0, -1, 0);
     const int d1 = near(1, c1, 1, 0);
@@ -391,18 +388,18 @@ ps_border_kernel(const uint8_t* __restrict__ mask, uint8_t* __restrict__ border,
 // The sums run over the lanes of a wave, not in the source's raster order: float64, equal to the
 // last bits only.
 template <typename T, int PW>
-__global__ void __launch_bounds__(1024)
+__global__ void __launch_bounds__(kPsWaves * 64)
 ps_sweep_kernel(T* grid, uint8_t* mask, uint8_t* border, int gx, int gy, long pitch, int k,
                 double half_power) {
   IPA_NO_FMA
   extern __shared__ int ps_prog[];
   volatile int* prog = ps_prog;
-  for (int r = threadIdx.x; r < gx; r += 1024) ps_prog[r] = 0;
+  for (int r = threadIdx.x; r < gx; r += kPsWaves * 64) ps_prog[r] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const volatile uint8_t* vmask = mask;
   const volatile T* vgrid = grid;
-  for (int i = wave; i < gx; i += 16) {
+  for (int i = wave; i < gx; i += kPsWaves) {
     for (int j0 = 0; j0 < gy; j0 += 64) {
       const int jl = j0 + lane;
       unsigned long long bits = __builtin_amdgcn_ballot_w64(jl < gy && border[(long)i * gy + jl] != 0);
@@ -476,7 +473,7 @@ int ipa_unstructured_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, int h, int w
   int rc = ipa_tab_upload(ctx, pts.data(), pts.size() * 8, &d);
   if (rc) return rc;
   dim3 grid((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)), block(256);
-  const int pw = power == 2.0 ? 2 : (power == 1.0 ? 1 : 0);
+  const int pw = idw_power_pick(power);
   return by_float(dtype, [&](auto t) {
     using T = decltype(t);
     return pick_or_last<2, 1, 0>(pw, [&](auto PW) {
@@ -500,7 +497,7 @@ int ipa_circular_idw_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8
   const int segs_x = (h + 63) / 64;
   const long segs = (long)segs_x * h;
   dim3 grid((unsigned)((segs + 3) / 4)), block(256);
-  const int pw = power == 2.0 ? 2 : (power == 1.0 ? 1 : 0);
+  const int pw = idw_power_pick(power);
   int rc = ipa_plan_reserve(ctx, (size_t)h * h * sizeof(double2));
   if (rc) return rc;
   double2* polar = (double2*)ctx->plan;
@@ -594,7 +591,7 @@ int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_m
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, d_grid && d_mask, "null pointer");
   IPA_REQUIRE(ctx, h > 0 && w > 0 && pitch >= w && ksize >= 0, "bad shape/ksize");
-  IPA_REQUIRE(ctx, h <= 16000, "point spread IDW keeps one progress word per row in LDS: at most 16000 rows");
+  IPA_REQUIRE(ctx, point_spread_rows_ok(h), "point spread IDW keeps one progress word per row in LDS: at most %d rows", kPsMaxRows);
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "point_spread_idw supports float32/float64 grids (got dtype %d)", dtype);
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -607,7 +604,7 @@ int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_m
   IPA_HIP(ctx, hipMemsetAsync(border, 0, bb + 256, ctx->stream));
   const unsigned nb = (unsigned)(((long)h * w + 255) / 256);
   const double hp = 0.5 * power;
-  const int pw = power == 2.0 ? 2 : (power == 1.0 ? 1 : 0);
+  const int pw = idw_power_pick(power);
   const size_t lds = (size_t)h * sizeof(int);
   for (long n = 0;; n++) {
     // _createBorder; its return value decides whether another sweep runs
@@ -621,7 +618,7 @@ int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_m
     rc = by_float(dtype, [&](auto t) {
       using T = decltype(t);
       return pick_or_last<2, 1, 0>(pw, [&](auto PW) {
-        return launch(ctx, ps_sweep_kernel<T, PW()>, dim3(1), dim3(1024), lds, d_grid, d_mask, border,
+        return launch(ctx, ps_sweep_kernel<T, PW()>, dim3(1), dim3(kPsWaves * 64), lds, d_grid, d_mask, border,
                       h, w, pitch, ksize, hp);
       });
     });
@@ -642,6 +639,49 @@ int ipa_point_spread_idw(ipa_ctx* ctx, void* grid, int dtype, uint8_t* mask, int
   // the mask is modified too (filled pixels are unmasked)
   IPA_HIP(ctx, hipMemcpyAsync(mask, dm, (size_t)h * w, hipMemcpyDeviceToHost, ctx->stream));
   return ipa_fill_back(ctx, grid, dg, gb);
+}
+
+// the constants and predicates of this file and of resize.hip: interp_paths.hpp
+int ipa_interp_path(int op, double a, double b, double c, double d) {
+  const auto in_int = [](double v) { return v >= -2147483648.0 && v <= 2147483647.0 && v == (double)(long)v; };
+  if (op != IPA_INTERP_POWER && op != IPA_INTERP_RESIZE_VEC4 && !(in_int(a) && in_int(b) && in_int(c) && in_int(d)))
+    return -1;
+  const int ia = (int)a, ib = (int)b, ic = (int)c, id = (int)d;
+  switch (op) {
+    case IPA_INTERP_CONST:
+      switch (ia) {
+        case IPA_INTERP_K_CROSS_SEG: return kCrossSeg;
+        case IPA_INTERP_K_CROSS_BALLOT_STEPS: return kCrossBallotSteps;
+        case IPA_INTERP_K_CROSS_SEARCH_PASS: return kCrossSearchPass;
+        case IPA_INTERP_K_FASTDIV_SHIFT: return kFastDivShift;
+        case IPA_INTERP_K_PS_WAVES: return kPsWaves;
+        case IPA_INTERP_K_PS_MAX_ROWS: return kPsMaxRows;
+        case IPA_INTERP_K_STAT_MAX: return kStatMax;
+      }
+      return -1;
+    case IPA_INTERP_CROSS_FASTDIV: return ia >= 0 && ib >= 1 ? (int)cross_fastdiv(ia, ib) : -1;
+    case IPA_INTERP_CIRCULAR_FASTDIV: return ia >= 0 && ib >= 0 ? (int)circular_fastdiv(ia, ib) : -1;
+    case IPA_INTERP_FASTDIV_MUL: return ia >= 1 ? (int)fastdiv_mul(ia) : -1;
+    case IPA_INTERP_POWER: return idw_power_pick(a);
+    case IPA_INTERP_POINT_SPREAD_ROWS: return ia >= 1 ? (int)point_spread_rows_ok(ia) : 0;
+    case IPA_INTERP_STAT_SAMPLES:
+      if (ia < 1 || ib < 1) return -1;
+      return fast_stat_fits(ia, ib) ? (int)fast_stat_per_axis(ia, ib) : 0;
+    case IPA_INTERP_RESIZE_VEC4: {
+      if (!in_int(a) || !in_int(b) || !(c >= 0 && c == (double)(long)c) || !(d >= 0 && d == (double)(long)d)) return -1;
+      if (!interp_float(ia)) return 0;
+      return resize_vec4(ib, (long)c, (uintptr_t)d, 0, ipa_dtype_size(ia)) ? 1 : 2;
+    }
+    case IPA_INTERP_RESIZE_AREA: {
+      if (ia < 1 || ib < 1 || ic < 1 || id < 1) return -1;
+      int isx = 0, isy = 0;
+      return resize_area_path(resize_scale(ib, id), resize_scale(ia, ic), &isx, &isy);
+    }
+    case IPA_INTERP_RESIZE_LINEAR:
+      if (ia < 1 || ib < 1 || ic < 1 || id < 1) return -1;
+      return resize_linear_is_area(ia, ib, ic, id) ? 1 : 2;
+  }
+  return -1;
 }
 
 }  // extern "C"

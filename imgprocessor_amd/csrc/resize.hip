@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "interp_paths.hpp"
 #include "launch.hpp"
 
 #define IPA_NO_FMA _Pragma("clang fp contract(off)")
@@ -163,7 +164,7 @@ area_kernel(const T* __restrict__ src, long spitch, T* __restrict__ dst, long dp
 }
 
 // ------------------------------------------------------------- fastFilter's statistics --
-constexpr int kStatMax = 4096;   // window elements a wave keeps in LDS (doubles)
+// (kStatMax window elements per wave in LDS: interp_paths.hpp)
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -321,8 +322,7 @@ static int launch_separable(ipa_ctx* ctx, int ks, const void* src, long spitch, 
                             const float* alpha, int xmax, const int* yofs, const float* beta) {
   dim3 block(256), gh((unsigned)((dw + 255) / 256), (unsigned)sh), gv((unsigned)((dw + 255) / 256), (unsigned)dh);
   dim3 gv4((unsigned)((dw / 4 + 255) / 256), (unsigned)dh);
-  const bool vec4 = dw % 4 == 0 && dpitch % 4 == 0 && (uintptr_t)dst % (4 * sizeof(T)) == 0 &&
-                    (uintptr_t)tmp % (4 * sizeof(T)) == 0;
+  const bool vec4 = resize_vec4(dw, dpitch, (uintptr_t)dst, (uintptr_t)tmp, sizeof(T));
   return pick_or_last<2, 4, 8>(ks, [&](auto KS) {
     const int rc = launch(ctx, hresize_kernel<T, KS()>, gh, block, 0, src, spitch, sh, sw, tmp, dw,
                           xofs, alpha, xmax);
@@ -347,23 +347,23 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "resize is built for float32 / float64 images (cv2's 8-bit fixed-point "
                          "paths differ between OpenCV versions); got dtype %d", dtype);
-  const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
+  const double scale_x = resize_scale(sw, dw), scale_y = resize_scale(sh, dh);
   const size_t es = ipa_dtype_size(dtype);
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   dim3 block(256), grid((unsigned)((dw + 255) / 256), (unsigned)dh);
-  // OpenCV's rule (resize.cpp): INTER_LINEAR at an exact 2 x 2 reduction IS the area average
-  // ("interpolation == INTER_LINEAR && is_area_fast && iscale_x == 2 && iscale_y == 2")
-  if (interp == IPA_RESIZE_LINEAR && sw == 2 * dw && sh == 2 * dh) interp = IPA_RESIZE_AREA;
+  // (OpenCV's rule: INTER_LINEAR at an exact 2 x 2 reduction IS the area average)
+  if (interp == IPA_RESIZE_LINEAR && resize_linear_is_area(sh, sw, dh, dw)) interp = IPA_RESIZE_AREA;
   if (interp != IPA_RESIZE_LINEAR && interp != IPA_RESIZE_CUBIC && interp != IPA_RESIZE_AREA &&
       interp != IPA_RESIZE_LANCZOS4)
     IPA_UNSUPPORTED(ctx, "resize: interpolation %d is not built (linear 1, cubic 2, area 3, "
                          "lanczos4 4; INTER_NEAREST and the exact / bit-exact variants are not)", interp);
   if (interp == IPA_RESIZE_AREA) {
-    if (!(scale_x >= 1 && scale_y >= 1))
+    int isx = 0, isy = 0;
+    const int area = resize_area_path(scale_x, scale_y, &isx, &isy);
+    if (!area)
       IPA_UNSUPPORTED(ctx, "INTER_AREA is built for downscaling (OpenCV switches to a bilinear "
                            "variant when enlarging)");
-    const int isx = (int)nearbyint(scale_x), isy = (int)nearbyint(scale_y);
-    if (fabs(scale_x - isx) < DBL_EPSILON && fabs(scale_y - isy) < DBL_EPSILON) {
+    if (area == 1) {
       return by_float(dtype, [&](auto t) {
         return launch(ctx, area_fast_kernel<decltype(t)>, grid, block, 0, d_src, src_pitch, sh, sw,
                       d_dst, dst_pitch, dh, dw, isx, isy);
@@ -461,8 +461,8 @@ int ipa_fast_filter_stat_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, 
               "bad arguments");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "fast_filter_stat supports float32/float64 arrays (got dtype %d)", dtype);
-  const long per_axis = (2L * ksize + every - 1) / every;
-  if (per_axis * per_axis > kStatMax)
+  const long per_axis = fast_stat_per_axis(ksize, every);
+  if (!fast_stat_fits(ksize, every))
     IPA_UNSUPPORTED(ctx, "fast_filter_stat: %ld x %ld window samples exceed the %d a wave keeps in "
                          "LDS (raise `every`)", per_axis, per_axis, kStatMax);
   const int n0 = (h + every - 1) / every, n1 = (w + every - 1) / every;

@@ -496,6 +496,43 @@ int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_m
 int ipa_point_spread_idw(ipa_ctx* ctx, void* grid, int dtype, uint8_t* mask, int h, int w,
                          int ksize, double power, long max_iter);
 
+/* The constants and predicates by which the kernels and launchers behind the four fills above,
+ * ipa_resize_dev and ipa_fast_filter_stat_dev choose a branch or a kernel (csrc/interp_paths.hpp:
+ * the code they call), without a context or a device.  Arguments are doubles that hold integers
+ * (a power and a byte address fit too); returns -1 for an unknown op or an argument out of range. */
+typedef enum {
+  IPA_INTERP_CONST = 0,            /* a = ipa_interp_const */
+  IPA_INTERP_CROSS_FASTDIV = 1,    /* a = nt window positions, b = ny window columns: 1 when
+                                      cross_local_avg_kernel takes t / ny by multiply-shift */
+  IPA_INTERP_CIRCULAR_FASTDIV = 2, /* a = nx, b = ny window rows / columns: the same for
+                                      circular_idw_kernel (t < nx ny) */
+  IPA_INTERP_FASTDIV_MUL = 3,      /* a = ny: the multiplier M = ceil(2^shift / ny) */
+  IPA_INTERP_POWER = 4,            /* a = power: 2 / 1 the kernels without pow, 0 the generic one */
+  IPA_INTERP_POINT_SPREAD_ROWS = 5,/* a = h: 1 runs, 0 refused (one LDS word per row) */
+  IPA_INTERP_STAT_SAMPLES = 6,     /* a = ksize, b = every: window samples per axis,
+                                      ceil(2 ksize / every), or 0 when their square exceeds the
+                                      wave's LDS buffer and the call is refused */
+  IPA_INTERP_RESIZE_VEC4 = 7,      /* a = dtype, b = dw, c = dst_pitch (elements), d = byte address
+                                      of the destination (OR-ed with that of the intermediate
+                                      rows, which the library allocates 256-byte aligned):
+                                      1 vresize4_kernel, 2 vresize_kernel, 0 not a float dtype */
+  IPA_INTERP_RESIZE_AREA = 8,      /* a, b, c, d = sh, sw, dh, dw: 0 refused (enlarging),
+                                      1 area_fast_kernel (integer scales), 2 area_kernel */
+  IPA_INTERP_RESIZE_LINEAR = 9     /* a, b, c, d = sh, sw, dh, dw: 1 the exact 2 x 2 reduction,
+                                      which runs as INTER_AREA, 2 the separable kernels */
+} ipa_interp_op;
+typedef enum {
+  IPA_INTERP_K_CROSS_SEG = 0,          /* pixels of a row per wave of the cross-average fill */
+  IPA_INTERP_K_CROSS_BALLOT_STEPS = 1, /* steps of each search taken from the first ballot */
+  IPA_INTERP_K_CROSS_SEARCH_PASS = 2,  /* steps per pass of the further search; columns / rows per
+                                          chunk of the stale-slot tables */
+  IPA_INTERP_K_FASTDIV_SHIFT = 3,
+  IPA_INTERP_K_PS_WAVES = 4,           /* waves (= rows in flight) of the point-spread sweep */
+  IPA_INTERP_K_PS_MAX_ROWS = 5,
+  IPA_INTERP_K_STAT_MAX = 6            /* window samples a wave of the statistics kernel keeps */
+} ipa_interp_const;
+int ipa_interp_path(int op, double a, double b, double c, double d);
+
 /* ---------------------------------------------------------------- filters: fast* */
 /* replaces cv2.resize(img, (dw, dh), interpolation=...) at filters/fastFilter.py:47-48
  * (INTER_LANCZOS4 on the float64 grid of statistics) and filters/fastMean.py:14-19 (INTER_AREA

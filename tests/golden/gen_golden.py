@@ -831,11 +831,12 @@ def _resize_axis_np(ssize, dsize, kind, clamp_x):
     else:
         s45 = 0.70710678118654752440084436210485
         cs = np.array([[1, 0], [-s45, -s45], [0, 1], [s45, -s45], [-1, 0], [s45, s45], [0, -1], [-s45, s45]])
-        x = f.astype(np.float64)
-        y0 = -(x + 3) * np.pi * 0.25
+        # (OpenCV's x is a float: x + 3 and x + 3 - i are float32 sums before they meet the double pi)
+        x3 = f + np.float32(3)
+        y0 = -x3.astype(np.float64) * np.pi * 0.25
         s_, c_ = np.sin(y0), np.cos(y0)
         i = np.arange(8)
-        y = -(x[:, None] + 3 - i[None, :]) * np.pi * 0.25
+        y = -(x3[:, None] - i[None, :].astype(np.float32)).astype(np.float64) * np.pi * 0.25
         with np.errstate(divide='ignore', invalid='ignore'):
             co = ((cs[None, :, 0] * s_[:, None] + cs[None, :, 1] * c_[:, None]) / (y * y)).astype(np.float32)
         tot = np.zeros(dsize, np.float32)

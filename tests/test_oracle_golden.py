@@ -605,18 +605,15 @@ def cv_resize_cases(g):
 
 def test_cv_resize_independent_restatement(oracle):
     """cv2.resize: oracle.c against the second, vectorised numpy restatement
-    (tests/golden/gen_golden.py::resize_np).  Bilinear, bicubic and both INTER_AREA forms agree bit
-    for bit; Lanczos4 to the last bits of the float32 coefficients (numpy's vectorised sin / cos
-    against libm's, as for the remap table in cv_modes.npz)."""
+    (tests/golden/gen_golden.py::resize_np).  Every mode agrees bit for bit, Lanczos4 included:
+    OpenCV's interpolateLanczos4 takes a float x, so x + 3 - i is a float32 sum before it meets
+    the double pi - in oracle.c and in resize_np alike."""
     g, pin = load_cv_golden('cv_resize.npz')
     print(pin)
     n = 0
     for key, src, dsize, kind, oid in cv_resize_cases(g):
         got = oracle.resize(src, dsize, oid)
-        if kind == 'lanczos4':
-            assert_close(got, g[key], 0, 2e-6, key)
-        else:
-            assert np.array_equal(got, g[key]), key
+        assert np.array_equal(got, g[key]), key
         n += 1
     assert n == 34
 
