@@ -20,17 +20,9 @@ static void fused_big_launch_one(ipa_ctx* ctx, const FusedCall& f) {
   WaveBigArgs<Src, K> a;
   for (int i = 0; i < K; i++)
     for (int j = 0; j < 12; j++) a.wrows[i][j] = j < K ? (float)f.kernel[i * K + j] : 0.f;
-  Src& s = a.src;
-  s.coord = f.map;
-  s.src = f.src; s.src_frame_bytes = f.src_frame_bytes; s.src_bytes = f.src_bytes;
-  s.sh = f.sh; s.sw = f.sw; s.spitch = f.spitch;
-  s.border = f.border; s.q5 = f.q5; s.cubic_a = f.cubic_a; s.lanczos = nullptr;
-  s.cval = (float)f.cval; s.ccval = (float)f.conv_cval; s.map_vec = f.map_vec;
+  fused_source(a.src, f, f.map);
   a.p = f.p;
-  using G = wave_geom<K>;
-  a.p.strips_x = (a.p.dw + G::OW - 1) / G::OW;
-  a.p.strip_h = wave_strip_height(ctx, a.p.dh, a.p.dw, f.n_frames, K, true, 0, a.p.strips_x);
-  a.p.strips = (unsigned)a.p.strips_x * (unsigned)((a.p.dh + a.p.strip_h - 1) / a.p.strip_h);
+  wave_strips(ctx, a.p, wave_geom<K>::OW, f.n_frames, K, true, 0);
   dim3 grid = wave_grid(ctx, a.p, f.n_frames, IPA_WPB, true, coord_is_table<typename Src::coord_type>::value, false, K),
        block(64 * IPA_WPB);
   hipLaunchKernelGGL((wave_stencil_big_kernel<Src, K>), grid, block, 0, ctx->stream, a);
@@ -38,18 +30,15 @@ static void fused_big_launch_one(ipa_ctx* ctx, const FusedCall& f) {
 
 }  // namespace ipa
 
-// returns 1 when the call is not covered (the caller then runs remap and filter as two launches)
+// map-based bilinear remaps: float32 frames with 7 / 9 / 11 taps, uint16 frames with 7 (fused.hip::dense_route)
 int ipa_fused_big_launch(ipa_ctx* ctx, const ipa::FusedCall& f, int K) {
   using namespace ipa;
-  if (f.dst_dt != IPA_F32 || f.coord_kind != 0 || f.interp_base != IPA_INTER_LINEAR) return 1;
-  if (K == 7 && f.src_dt == IPA_U16) {
-    fused_big_launch_one<uint16_t, kLinear, 7>(ctx, f);
-    return 0;
-  }
-  if (f.src_dt != IPA_F32) return 1;
-  if (K == 7) fused_big_launch_one<float, kLinear, 7>(ctx, f);
+  if (f.dst_dt != IPA_F32 || f.coord_kind != 0 || f.interp_base != IPA_INTER_LINEAR) return kNotCovered;
+  if (f.src_dt == IPA_U16 && K == 7) fused_big_launch_one<uint16_t, kLinear, 7>(ctx, f);
+  else if (f.src_dt != IPA_F32) return kNotCovered;
+  else if (K == 7) fused_big_launch_one<float, kLinear, 7>(ctx, f);
   else if (K == 9) fused_big_launch_one<float, kLinear, 9>(ctx, f);
   else if (K == 11) fused_big_launch_one<float, kLinear, 11>(ctx, f);
-  else return 1;
+  else return kNotCovered;
   return 0;
 }

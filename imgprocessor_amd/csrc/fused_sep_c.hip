@@ -23,14 +23,12 @@ template <typename T> static int strip_remap_int_launch(ipa_ctx* ctx, const ipa:
     if (!p.frames_wg) return 1;
   }
   Src s;
-  s.coord = f.map;
-  s.src_frame_bytes = f.src_frame_bytes; s.src_bytes = f.src_bytes;
-  s.sh = f.sh; s.sw = f.sw; s.spitch = f.spitch;
-  s.border = f.border; s.q5 = 1; s.cubic_a = f.cubic_a; s.lanczos = nullptr;
-  s.cval = (float)f.cval; s.ccval = 0.f; s.map_vec = f.map_vec;
+  fused_source(s, f, f.map);
+  s.q5 = 1;       // cv2's 1/32-px coordinates, whatever the flag
+  s.ccval = 0.f;  // no filter
   const double one = 1.0;
   for (int i = 0; i < parts; i++) {
-    s.src = part[i].src;
+    s.src = part[i].src;   // (per part)
     launch_sep<Src, 1, T>(ctx, part[i].p, s, &one, &one, part[i].n_frames, 0.f);
   }
   return 0;

@@ -21,31 +21,13 @@ struct FusedSep {
 };
 
 template <typename ST, int INTERP, typename Coord, int K>
-static void fused_sep_one(ipa_ctx* ctx, const FusedCall& f, const Coord& c, const FusedSep& q) {
-  using Src = SampleRowSrc<ST, INTERP, Coord>;
-  FusedCall part[2];   // (the plan and the stored coordinates as in fused_impl.hpp::fused_launch_one)
-  const SharedPlan plan = fused_plan(ctx, sep_shared<Src, K>::value, f, part);
-  if constexpr (std::is_same<Coord, HomographyCoord>::value && sep_shared<Src, K>::value) {
-    if (ctx->tune.stored_coords > 0 && f.n_frames >= ctx->tune.stored_coords && plan != kPerFrameLoop) {
-      StoredCoord<double> sc;
-      if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0) {
-        fused_sep_one<ST, INTERP, StoredCoord<double>, K>(ctx, f, sc, q);
-        return;
-      }
-    }
-  }
-  if (plan == kSharedSplit) {
-    fused_sep_one<ST, INTERP, Coord, K>(ctx, part[0], c, q);
-    fused_sep_one<ST, INTERP, Coord, K>(ctx, part[1], c, q);
-    return;
-  }
-  Src s;
-  s.coord = c;
-  s.src = f.src; s.src_frame_bytes = f.src_frame_bytes; s.src_bytes = f.src_bytes;
-  s.sh = f.sh; s.sw = f.sw; s.spitch = f.spitch;
-  s.border = f.border; s.q5 = f.q5; s.cubic_a = f.cubic_a; s.lanczos = nullptr;
-  s.cval = (float)f.cval; s.ccval = (float)f.conv_cval; s.map_vec = f.map_vec;
-  launch_sep<Src, K>(ctx, f.p, s, q.ky, q.kx, f.n_frames, q.xcval);
+static void fused_sep_one(ipa_ctx* ctx, const FusedCall& call, const Coord& coord, const FusedSep& q) {
+  fused_batch<ST, INTERP, K, sep_shared>(ctx, call, coord, [ctx, &q](const FusedCall& f, const auto& c, SharedPlan) {
+    using Src = SampleRowSrc<ST, INTERP, std::decay_t<decltype(c)>>;
+    Src s;
+    fused_source(s, f, c);
+    launch_sep<Src, K>(ctx, f.p, s, q.ky, q.kx, f.n_frames, q.xcval);
+  });
 }
 
 template <typename Coord, int K>

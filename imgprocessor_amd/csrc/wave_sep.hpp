@@ -402,13 +402,11 @@ wave_sep_kernel(WaveParams p, Src src, SepTaps<K> w, float xcval) {
 
 // strip geometry and grid of a launch of wave_sep_kernel<Src, K> (p.frames_wg: the launch is on the shared-record loop)
 template <typename Src, int K> static dim3 sep_grid(ipa_ctx* ctx, WaveParams& p, int n_frames) {
-  p.strips_x = (p.dw + sep_geom<K>::OW - 1) / sep_geom<K>::OW;
   // the tall strips of the shared-record loop only where that loop runs (see fused_impl.hpp::fused_launch_one); plain
   // rows: the short strips of the plain dense filters (64 x 4K, 9 + 9 taps: 72 rows 0.906, 24 rows 0.882 ms)
   const bool shared_run = shared_loop_plan(ctx, sep_shared<Src, K>::value, n_frames, true) == kSharedLoop;
-  p.strip_h = wave_strip_height(ctx, p.dh, p.dw, n_frames, K, false,
-                                shared_run ? 2 : (std::is_same<Src, LoadRowSrc>::value ? 1 : 0), p.strips_x);
-  p.strips = (unsigned)p.strips_x * (unsigned)((p.dh + p.strip_h - 1) / p.strip_h);
+  wave_strips(ctx, p, sep_geom<K>::OW, n_frames, K, false,
+              shared_run ? 2 : (std::is_same<Src, LoadRowSrc>::value ? 1 : 0));
   // plain rows (LoadRowSrc): frames share nothing - frame after frame, every XCD streaming through frames of its
   // own (knob frame_major, as the dense plain filters since round 4)
   return wave_grid(ctx, p, n_frames, 4, true, sep_shares_maps<Src>::value, std::is_same<Src, LoadRowSrc>::value, -K);

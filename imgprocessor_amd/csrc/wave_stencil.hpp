@@ -1018,4 +1018,13 @@ static inline int wave_strip_height(const ipa_ctx* ctx, int dh, int dw, int n_fr
   return 8;
 }
 
+// the strip setup of a launch: strips per row in steps of `ow` px (the OW of the kernel's wave_geom / sep_geom), their
+// height (wave_strip_height with the caller's fma_bound / piped) and the strips per frame
+static inline void wave_strips(const ipa_ctx* ctx, WaveParams& p, int ow, int n_frames, int K, bool fma_bound,
+                               int piped) {
+  p.strips_x = (p.dw + ow - 1) / ow;
+  p.strip_h = wave_strip_height(ctx, p.dh, p.dw, n_frames, K, fma_bound, piped, p.strips_x);
+  p.strips = (unsigned)p.strips_x * (unsigned)((p.dh + p.strip_h - 1) / p.strip_h);
+}
+
 }  // namespace ipa

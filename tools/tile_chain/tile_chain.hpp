@@ -32,6 +32,9 @@
 // waves at 3 workgroups per CU instead of at stream rate in wave_sep.hpp (profiles/r05_micro.txt).
 #pragma once
 
+#include <utility>
+
+#include "fused_impl.hpp"   // ChainArgs
 #include "tile_warp.hpp"
 
 namespace ipa {
@@ -512,3 +515,50 @@ int tile_chain_run(hipStream_t stream, const TileChainArgs& t, const HomographyC
                    int K, unsigned grid, size_t lds);
 
 }  // namespace ipa
+
+// tile_chain.hip: 0 = launched, 1 = not a chain for that kernel
+int ipa_tile_chain_launch(ipa_ctx* ctx, const void* d_src, int sh, int sw, long src_pitch, const double* M,
+                          const double* ky, const double* kx, int K, void* d_dst, int dh, int dw,
+                          long dst_pitch, int n_frames, long src_frame_stride, long dst_frame_stride,
+                          int interp, int border_mode, double border_value, int cby, int cbx);
+
+// fused.hip's hook (perspective warp + separable filter, before the product's own routes; `rotated`: the product would
+// take the two launches for the angle).  0: launched, 1: not taken - the caller goes on -, < 0: an error.
+// knob tile_chain = 1: the chains that take two launches - bicubic warps, bilinear warps that rotate
+// the picture - in ONE launch on the tile skeleton.  Built for the review of round 4, bit-identical, and slower than
+// the two launches (16 x 4K + 9 + 9: bicubic 0.80 against 0.55 ms, rotated bilinear 0.87 against 0.56): the warp kernel
+// is bound by its vector work, not by the 8 B/px of workspace traffic the fusion saves, and the filter passes join it
+// in the same waves instead of running at stream rate in a kernel of their own.  Off by default; only calls the two
+// launches would accept go there (anything else falls through to their checks).
+static inline int tile_chain_try(ipa_ctx* ctx, const ipa::ChainArgs& a, const double* M, const double* ky, int nky,
+                                 const double* kx, int nkx, bool rotated) {
+  const int base = a.interp & 0xff;
+  const bool cubic = base == IPA_INTER_CUBIC_CV || base == IPA_INTER_CUBIC_KEYS;
+  auto mode_ok = [](int b) { return b >= IPA_BORDER_CONSTANT && b <= IPA_BORDER_REFLECT101; };
+  const bool valid = a.src && a.dst && a.src != a.dst && ky && kx && nky == nkx && a.src_dtype == IPA_F32 &&
+                     a.dst_dtype == IPA_F32 && a.sh > 0 && a.sw > 0 && a.dh > 0 && a.dw > 0 && a.src_pitch >= a.sw &&
+                     a.dst_pitch >= a.dw && a.src_pitch < (1l << 23) && a.n_frames >= 1 && a.n_frames <= 65535 &&
+                     (a.interp & ~(0xff | IPA_INTER_Q5)) == 0 && mode_ok(a.border_mode) &&
+                     mode_ok(a.conv_border_y) && mode_ok(a.conv_border_x);
+  // (the two launches may write over their source - the warp has read it all by then; one launch may not)
+  auto span = [](const void* p0, long frames, long stride, long pitch, int h, int w) {
+    const char* lo = (const char*)p0;
+    return std::pair<const char*, const char*>(lo, lo + ((frames - 1) * stride + (long)(h - 1) * pitch + w) * 4);
+  };
+  bool apart = false;
+  if (valid && a.src_frame_stride >= 0 && a.dst_frame_stride >= 0) {
+    const auto s = span(a.src, a.n_frames, a.src_frame_stride, a.src_pitch, a.sh, a.sw);
+    const auto d = span(a.dst, a.n_frames, a.dst_frame_stride, a.dst_pitch, a.dh, a.dw);
+    apart = s.second <= d.first || d.second <= s.first;
+  }
+  // (1: the chains that take two launches - bicubic, rotated bilinear; 2: every chain the kernel covers, upright
+  // bilinear ones included, which the fused strip kernel already runs in one launch - the tests' value)
+  if (!(ctx->tune.tile_chain && valid && apart &&
+        (cubic || (base == IPA_INTER_LINEAR && (rotated || ctx->tune.tile_chain >= 2)))))
+    return 1;
+  const int rc = ipa_tile_chain_launch(ctx, a.src, a.sh, a.sw, a.src_pitch, M, ky, kx, nky, a.dst, a.dh, a.dw, a.dst_pitch,
+                                       a.n_frames, a.src_frame_stride, a.dst_frame_stride, a.interp, a.border_mode,
+                                       a.border_value, a.conv_border_y, a.conv_border_x);
+  if (rc == 0) IPA_HIP(ctx, hipGetLastError());
+  return rc;
+}
