@@ -1,11 +1,17 @@
 """CPU: the numpy restatement of scikit-image 0.18's non-local means (tests/nlm_ref.py) against
 the fixture tests/golden/nlm.npz (written by tests/golden/gen_nlm_golden.py where skimage exists,
 after it has pinned the restatement to skimage through skimage's own fast_exp), and the argument
-checks of ops.nl_means, which run before any device is touched."""
+checks of ops.nl_means, which run before any device is touched.
+
+The geometry table of nlm_ref.py (patch sizes 2 ... 5 and 8 ... 11 on frames one past each tile
+edge) is proven here to reach every instantiation of nlm_kernel with more than one workgroup in x
+and in y in both types, to denoise something with no pixel near the cut-off, and to tell wrong
+variants of the restatement from the right one under the float32 tolerance of test_gpu_nlm.py."""
 import numpy as np
 import pytest
 
 from .conftest import load_golden
+from . import nlm_ref as nr
 from .nlm_ref import nlm_ref
 
 G = load_golden('nlm.npz')
@@ -67,3 +73,66 @@ def test_arguments_are_checked_before_a_device_is_touched(monkeypatch):
     from imgprocessor_amd.filters import denoiseNLMeans
     with pytest.raises(TypeError):
         denoiseNLMeans([[0.0, 1.0], [1.0, 0.0]])
+
+
+def test_geometry_table_reaches_every_instantiation():
+    """the control: before this table patch sizes 2 / 3 and 8 / 9 were launched by no test, 4 / 5
+    and 10 / 11 with one workgroup only.  Now every nlm_kernel<T, W> has a case with more than one
+    workgroup in x and one in y in both types, at the edge of its 64-row tile (float32), of its
+    32-row tile (float64) and of its column tile"""
+    assert {nr.instantiation(s) for s in nr.GEO_SIZES} == {(2, 63), (4, 61), (8, 57), (10, 55)}
+    assert nr.instantiation(6) == nr.instantiation(7) == (6, 59)
+    for s in nr.GEO_SIZES:
+        assert nr.instantiation(s) == nr.instantiation(s | 1)
+        tx = nr.instantiation(s)[1]
+        shapes = nr.geo_shapes(s)
+        assert shapes == ((33, tx + 1), (65, tx), (64, 2 * tx + 1))
+        for dt in (np.float32, np.float64):
+            wg = [nr.workgroups(s, shp, dt) for shp in shapes]
+            assert max(x for x, y in wg) >= 3 and max(y for x, y in wg) >= 2, (s, dt, wg)
+            assert (1, 2 if dt == np.float32 else 3) in wg    # exactly one column tile
+        assert nr.workgroups(s, shapes[0], np.float32) == (2, 1)   # one column past the tile
+        assert nr.workgroups(s, shapes[0], np.float64) == (2, 2)   # one row past the 32-row tile
+        assert nr.workgroups(s, shapes[1], np.float32) == (1, 2)   # one row past the 64-row tile
+    assert len(nr.GEO_CASES) == 24
+
+
+def test_geometry_cases_denoise_and_stay_off_the_cut_off():
+    from .test_gpu_nlm import DELTA, ERR32, ERR64
+    w32 = w64 = 0.0
+    for s, n, sg in nr.GEO_CASES:
+        img, out, margin = nr.geo_case(s, n, sg)
+        rng = np.abs(img).max()
+        assert (margin < DELTA).mean() == 0.0, (s, n, sg)
+        assert np.abs(out - img).max() >= 0.1 * rng, 'nothing is denoised'
+        o32 = nlm_ref(img, s, nr.GEO_D, nr.GEO_H, sg, dtype=np.float32)[0]
+        w32 = max(w32, np.abs(o32 - out).max() / rng)
+        ol = nlm_ref(img, s, nr.GEO_D, nr.GEO_H, sg, dtype=np.longdouble)[0]
+        w64 = max(w64, float(np.abs(ol - out).max() / rng))
+    print('restatement in float32 against float64: %.3g of the range (ERR32 %.3g)' % (w32, ERR32))
+    print('restatement in float64 against long double: %.3g of the range (ERR64 %.3g)' % (w64, ERR64))
+    assert w32 <= ERR32
+    if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps:
+        assert 0 < w64 <= ERR64
+
+
+@pytest.mark.parametrize('variant', nr.VARIANTS)
+def test_wrong_variants_exceed_the_float32_tolerance(variant):
+    """over the new cases - the geometry table and the knife-edge image, whose distances are
+    integers and often equal the cut-off exactly - each wrong variant is further from the
+    restatement than the tolerance under which the device is held against it"""
+    from .test_gpu_nlm import TOL
+    worst = 0.0
+    for s, n, sg in nr.GEO_CASES:
+        if sg == 0.0 and variant == 'sigma_s2':
+            continue
+        img, out, margin = nr.geo_case(s, n, sg)
+        bad = nlm_ref(img, s, nr.GEO_D, nr.GEO_H, sg, variant=variant)[0]
+        worst = max(worst, np.abs(bad - out).max() / np.abs(img).max())
+    img = nr.knife_image()
+    out, margin = nlm_ref(img, **nr.KNIFE)
+    assert (margin == 0).mean() > 0.5 and margin[margin > 0].min() >= 1.0
+    bad = nlm_ref(img, variant=variant, **nr.KNIFE)[0]
+    worst = max(worst, np.abs(bad - out).max() / img.max())
+    print('%s: %.3g of the range (tolerance %.3g)' % (variant, worst, TOL[np.float32]))
+    assert worst > TOL[np.float32]

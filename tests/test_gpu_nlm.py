@@ -6,12 +6,16 @@ min_t |D - 5| is under DELTA set aside, as here):
   float32 frames: nlm_ref run in float32 against the float64 restatement   1.73e-6  -> x 4
   float64 frames: nlm_ref run in float64 against the same in long double   2.67e-15 -> x 4
 The factor 4 is headroom for the device exponential and the order of the sums.
+Re-measured over the 24 cases of the geometry table (nlm_ref.GEO_CASES, patch sizes 3, 5, 9 and
+11): 3.71e-7 and 7.61e-16, both under the figures above, which stay
+(test_cpu_nlm.py::test_geometry_cases_denoise_and_stay_off_the_cut_off asserts it).
 """
 import numpy as np
 import pytest
 
 from .conftest import load_golden, synth
 from .gpu_helpers import same_bits
+from . import nlm_ref as nr
 from .nlm_ref import nlm_ref
 
 pytestmark = pytest.mark.gpu
@@ -241,3 +245,106 @@ def test_nan_to_zero(ctx):
     d = ctx.to_device(a)
     assert ops.nan_to_zero(d) is d
     assert np.array_equal(d.get(), np.where(np.isnan(a), 0, a))
+
+
+# ------------------------------------------------- every instantiation at its tile edges ----
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('s,shape_no,sigma', nr.GEO_CASES)
+def test_instantiation_geometry(ctx, s, shape_no, sigma, dtype):
+    """nlm_kernel<T, 2 | 4 | 8 | 10> one row past its 64- and 32-row tiles and one column past its
+    column tile of 63 | 61 | 57 | 55, more than one workgroup in x and in y (test_cpu_nlm.py
+    proves it); the even patch size below gives the same bits"""
+    from imgprocessor_amd import ops
+    img, ref, margin = nr.geo_case(s, shape_no, sigma)
+    got = ops.nl_means(img.astype(dtype), s, nr.GEO_D, nr.GEO_H, sigma, ctx=ctx)
+    check(got, img, ref, margin, dtype, 's %d %s sigma %g' % (s, img.shape, sigma))
+    even = ops.nl_means(img.astype(dtype), s - 1, nr.GEO_D, nr.GEO_H, sigma, ctx=ctx)
+    assert np.array_equal(even.view(np.uint8), got.view(np.uint8)), 'patch size %d' % (s - 1)
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_cutoff_is_strict(ctx, dtype):
+    """an image of 0 and 4 at patch_size 5, h 0.8: every distance is an integer, computed exactly
+    in both types on both sides, and most pixels have one equal to 5 - which keeps its weight
+    exp(-5).  Nothing is set aside: there is no rounding that could switch a weight."""
+    from imgprocessor_amd import ops
+    img = nr.knife_image()
+    ref, margin = nlm_ref(img, **nr.KNIFE)
+    assert (margin == 0).any() and margin[margin > 0].min() >= 1.0
+    got = ops.nl_means(img.astype(dtype), nr.KNIFE['patch_size'], nr.KNIFE['patch_distance'], nr.KNIFE['h'],
+                       ctx=ctx)
+    worst = np.abs(got - ref).max() / img.max()
+    print('knife edge %s: worst %.2e of the range (tolerance %.2e)' % (np.dtype(dtype).name, worst, TOL[dtype]))
+    assert worst <= TOL[dtype]
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('s', [3, 7, 10])
+def test_patch_distance_0_and_1(ctx, s, dtype):
+    from imgprocessor_amd import ops
+    img = synth((37, 70), 95, np.float32)
+    got = ops.nl_means(img.astype(dtype), s, 0, 0.1, ctx=ctx)   # the self pair alone: the input
+    assert np.array_equal(got.view(np.uint8), img.astype(dtype).view(np.uint8))
+    ref, margin = ref_of(('d1', s), img, s, 1, 0.1)
+    got = ops.nl_means(img.astype(dtype), s, 1, 0.1, ctx=ctx)
+    check(got, img, ref, margin, dtype, 's %d d 1' % s)
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('s', [3, 11])
+def test_pitched_batch_small_and_large_patch(ctx, s, dtype):
+    """test_pitched_batch at the two ends of the patch sizes, on frames of two column tiles"""
+    from imgprocessor_amd import ops
+    from imgprocessor_amd.device import dtype_id
+    n, h, w = 2, 37, 70
+    src = np.stack([synth((h, w), 40 + i, np.float32) for i in range(n)]).astype(dtype)   # float32-exact
+    want = ops.nl_means(ctx.to_device(src), s, 3, 0.1).get()
+    sp, dp = w + 9, w + 5
+    sbig = np.full((n, h + 3, sp), 7.0, dtype)
+    sbig[:, :h, :w] = src
+    dbig = ctx.to_device(np.full((n, h + 2, dp), -5.0, dtype))
+    ctx._check(ctx._lib.ipa_nl_means_dev(ctx.handle, ctx.to_device(sbig).ptr, dtype_id(dtype), n, h, w, sp,
+                                         (h + 3) * sp, s, 3, 0.1, 0.0, dbig.ptr, dp, (h + 2) * dp), 'nl_means')
+    got = dbig.get()
+    assert np.array_equal(got[:, :h, :w].view(np.uint8), want.view(np.uint8))
+    assert (got[:, h:, :] == -5.0).all() and (got[:, :, w:] == -5.0).all(), 'wrote outside'
+    ref, margin = ref_of(('pitched', s), src[1].astype(np.float64), s, 3, 0.1)
+    check(got[1, :h, :w], src[1], ref, margin, dtype, 'pitched frame 1, s %d' % s)
+
+
+def _with_nans(shape, dtype, seed):
+    rng = np.random.default_rng(seed)
+    a = rng.standard_normal(shape).astype(dtype)
+    a[rng.random(shape) < 0.2] = np.nan
+    a.flat[0] = a.flat[-1] = np.nan
+    a[..., -1, :] = np.where(np.arange(shape[-1]) % 2, np.nan, a[..., -1, :])
+    return a
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('shape', [(1, 1), (4, 64), (5, 65), (9, 129), (3, 9, 70)])
+def test_nan_to_zero_shapes(ctx, shape, dtype):
+    from imgprocessor_amd import ops
+    a = _with_nans(shape, dtype, sum(shape))
+    a.flat[a.size // 2] = -0.0 if a.size > 2 else a.flat[a.size // 2]
+    d = ctx.to_device(a)
+    assert ops.nan_to_zero(d) is d
+    want = np.where(np.isnan(a), dtype(0), a)
+    assert np.array_equal(d.get().view(np.uint8), want.view(np.uint8))   # everything else keeps its bits
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_nan_to_zero_pitched(ctx, dtype):
+    """two frames in a buffer whose rows and frames are further apart than they are long: the
+    NaNs of the padding stay"""
+    from imgprocessor_amd.device import dtype_id
+    n, h, w, pitch, rows = 2, 9, 129, 140, 11
+    big = np.full((n, rows, pitch), np.nan, dtype)
+    a = _with_nans((n, h, w), dtype, 7)
+    big[:, :h, :w] = a
+    d = ctx.to_device(big)
+    ctx._check(ctx._lib.ipa_nan_to_zero_dev(ctx.handle, d.ptr, dtype_id(dtype), n, h, w, pitch, rows * pitch),
+               'nan_to_zero')
+    got = d.get()
+    assert np.array_equal(got[:, :h, :w].view(np.uint8), np.where(np.isnan(a), dtype(0), a).view(np.uint8))
+    assert np.isnan(got[:, h:, :]).all() and np.isnan(got[:, :, w:]).all(), 'the padding was touched'

@@ -2,12 +2,21 @@
 removeSinglePixels, bit-equal to the reference's outputs (tests/golden/ste.npz) and to the numpy
 restatement of test_cpu_ste.py on ragged sizes, a 4K frame, every frames-per-launch boundary,
 the threshold's special values, the decision's knife edge and pitched frames.
+
+The fuse and adjacency scenes of tests/ste_cases.py put a dependency chain of exactly `steps`
+pixels across every kind of tile border of every launch, and candidate pairs across every wave
+row boundary, the seam of the two ballot words, the output-tile borders and the image's edges;
+test_cpu_ste.py proves on the CPU which defect of the tile algorithm each of them sees.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from .conftest import load_golden
-from .test_cpu_ste import SteNumpy, bounded_nlf, same_f64
+from . import ste_cases as sc
+from .ste_cases import NLF, NLF8, random_scene as _scene
+from .test_cpu_ste import SteNumpy, bounded_nlf, remove_single_pixels, same_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -35,30 +44,6 @@ def _check(s, ref, what):
     assert np.array_equal(s.mask_clean, ref.mask_clean), what + ' mask_clean'
     if s.mask_STE is not None:
         assert np.array_equal(s.mask_STE, ref.mask_ste), what + ' mask_STE'
-
-
-def _scene(n, h, w, dtype, seed, nan=True):
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    base = 200 + 1500 * (x + y) / max(h + w - 2, 1)
-    f = base + 6 * rng.standard_normal((n, h, w))
-    f += (rng.random((n, h, w)) < 0.01) * 600                      # hits
-    f += (rng.random((n, h, w)) < 0.04) * rng.uniform(20, 60, (n, h, w))   # near the threshold
-    for k in range(n):                                              # pairs, so that some survive
-        ys, xs = rng.integers(0, h, 8), rng.integers(0, w, 8)
-        f[k, ys, xs] += 700
-        f[k, ys, np.minimum(xs + 1, w - 1)] += 700
-    if dtype == np.uint8:
-        f = f / 8
-    if np.dtype(dtype).kind == 'f':
-        if nan:
-            f[rng.random((n, h, w)) < 0.002] = np.nan
-        return f.astype(dtype)
-    return np.clip(np.round(f), 0, np.iinfo(dtype).max).astype(dtype)
-
-
-NLF = (3.0, 150.0, 1.1)
-NLF8 = (1.0, 20.0, 0.4)   # for uint8 frames (the scene / 8)
 
 
 def test_ste_golden(ctx):
@@ -274,3 +259,96 @@ def test_ste_continuation_launches(ctx, n_more, frames_per_launch):
     _bits(thr.get(), ref.thr, what + ' thr')
     assert np.array_equal(ste.get() != 0, ref.mask_ste), what + ' mask_STE'
     assert np.array_equal(clean.get() != 0, ref.mask_clean), what + ' mask_clean'
+
+
+# ------------------------------------------------------------ built scenes (ste_cases.py) ----
+def _check_dev(s, ref, what):
+    _bits(s.threshold.get(), ref.thr, what + ' thr')
+    _bits(s.noSTE.get(), ref.avg, what + ' noSTE')
+    assert np.array_equal(s.mask_STE.get() != 0, ref.mask_ste), what + ' mask_STE'
+    assert np.array_equal(s.mask_clean.get() != 0, ref.mask_clean), what + ' mask_clean'
+
+
+@pytest.mark.parametrize('steps', sc.FUSE_STEPS)
+def test_ste_fuses(ctx, steps):
+    """a chain of `st` pixels into the first and last output pixel of the tiles of every launch,
+    from all eight directions: every steps-per-launch from 1 to 8, and calls of 2 and 3 launches"""
+    fr, fuses, ref = sc.fuse_case(steps)
+    s = _S()(ctx.to_device(fr), sc.NLF_CONST, sc.NSTD_CONST, save_ste_indices=True)
+    _check_dev(s, ref, 'fuses, %d steps' % steps)
+    ste = s.mask_STE.get()
+    assert all(ste[f['P']] for f in fuses if f['kind'] != 'unlit')
+
+
+@pytest.mark.parametrize('n_more', sc.CONT_MORE)
+def test_ste_fuses_continuing(ctx, n_more):
+    """the same through ops.ste_update on a stored state: one launch (the state copied to the
+    workspace first), two, and three, under a caller mask that covers one link of some fuses"""
+    from imgprocessor_amd import DeviceArray, ops
+    fr, fuses, m, ref, hit = sc.cont_case(n_more)
+    h, w = sc.FUSE_HW
+    avg, thr = DeviceArray(ctx, (h, w), np.float64), DeviceArray(ctx, (h, w), np.float64)
+    cnt = DeviceArray.counts(ctx, (h, w))
+    ste, clean = DeviceArray(ctx, (h, w), np.uint8), DeviceArray(ctx, (h, w), np.uint8)
+    ctx._check(ctx._lib.ipa_memset(ctx.handle, ste.ptr, 0, ste.nbytes))
+    ops.ste_update(fr[:2], avg, cnt, thr, first_pair=True, nlf=sc.NLF_CONST, nstd=sc.NSTD_CONST,
+                   mask_ste=ste, mask_clean=clean)
+    ops.ste_update(ctx.to_device(fr[2:]), avg, cnt, thr, first_pair=False, mask=m, mask_ste=ste,
+                   mask_clean=clean)
+    what = 'fuses, %d more frames' % n_more
+    _bits(avg.get(), ref.avg, what + ' noSTE')
+    assert np.array_equal(cnt.get(), ref.count), what + ' count'
+    assert np.array_equal(ste.get() != 0, ref.mask_ste), what + ' mask_STE'
+    assert np.array_equal(clean.get() != 0, ref.mask_clean), what + ' mask_clean'
+
+
+@pytest.mark.parametrize('dtype', sc.ADJ_DTYPES)
+@pytest.mark.parametrize('st', sc.ADJ_STEPS)
+def test_ste_adjacency(ctx, st, dtype):
+    """pairs in all eight directions across every wave row boundary, the 63 | 64 seam, the
+    output-tile borders and the image's edges and corners, in step 0 and step 1 of a launch"""
+    fr, pairs, ref = sc.adj_case(st, dtype)
+    assert fr.dtype == dtype
+    s = _S()(ctx.to_device(fr), sc.NLF_CONST, sc.NSTD_CONST, save_ste_indices=True)
+    _check_dev(s, ref, 'pairs, %d steps, %s' % (st, np.dtype(dtype).name))
+
+
+def _rsp_input(shape, seed):
+    rng = np.random.default_rng(seed)
+    a = rng.random(shape) < 0.12
+    a.flat[0] = a.flat[-1] = True
+    if shape[1] > 64:
+        a[0, 63] = a[-1, 64] = True       # across two workgroups in x
+    if shape[0] > 4:
+        a[3, 1] = a[4, 2] = True          # and in y
+    return a
+
+
+@pytest.mark.parametrize('shape', [(1, 1), (1, 65), (5, 64), (4, 129), (9, 63)])
+def test_remove_single_pixels_shapes(ctx, shape):
+    from imgprocessor_amd import ops
+    a = _rsp_input(shape, shape[0] * 131 + shape[1])
+    want = remove_single_pixels(a)
+    assert np.array_equal(ops.remove_single_pixels(a, ctx=ctx), want)
+    d = ops.remove_single_pixels(ctx.to_device(a.astype(np.uint8) * 7))   # non-zero is set
+    assert d.dtype == np.uint8 and np.array_equal(d.get(), want.astype(np.uint8))
+
+
+def test_remove_single_pixels_pitched_and_in_place(ctx):
+    h, w, ip, op = 9, 129, 140, 133
+    a = _rsp_input((h, w), 5)
+    big = np.ones((h + 1, ip), np.uint8)       # set padding: a neighbour everywhere if read
+    big[:h, :w] = a
+    d_in = ctx.to_device(big)
+    d_out = ctx.to_device(np.full((h + 1, op), 9, np.uint8))
+    ctx._check(ctx._lib.ipa_remove_single_pixels_dev(ctx.handle, d_in.ptr, h, w, ip, d_out.ptr, op))
+    got = d_out.get()
+    assert np.array_equal(got[:h, :w], remove_single_pixels(a).astype(np.uint8))
+    assert (got[h:] == 9).all() and (got[:, w:] == 9).all(), 'wrote outside'
+    # in place, or overlapping by one row: refused on the host, nothing written
+    from imgprocessor_amd import _lib as L
+    assert ctx._lib.ipa_remove_single_pixels_dev(ctx.handle, d_in.ptr, h, w, ip, d_in.ptr, ip) == L.ERR_BAD_ARG
+    last_row = C.c_void_p(d_in.ptr.value + (h - 1) * ip)
+    assert ctx._lib.ipa_remove_single_pixels_dev(ctx.handle, d_in.ptr, h, w, ip, last_row, ip) == L.ERR_BAD_ARG
+    ctx.synchronize()
+    assert np.array_equal(d_in.get(), big)
