@@ -35,6 +35,7 @@ OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t
 _dp = C.POINTER(C.c_double)
+_ip = C.POINTER(C.c_int)
 
 # name -> argtypes; every function returns int (ipa_status) unless noted
 PROTOTYPES = {
@@ -71,6 +72,10 @@ PROTOTYPES = {
     'ipa_warp_perspective_dev': [_vp, _vp, _i, _i, _i, _l, _dp, _vp, _i, _i, _i, _l, _i, _l, _l,
                                  _i, _i, _d],
     'ipa_warp_perspective': [_vp, _vp, _i, _i, _i, _dp, _vp, _i, _i, _i, _i, _i, _i, _d],
+    'ipa_warp_grid_dev': [_vp, _vp, _i, _i, _i, _l, _ip, _dp, _i, _vp, _i, _i, _i, _l, _i, _l, _l,
+                          _i, _i, _d],
+    'ipa_warp_grid': [_vp, _vp, _i, _i, _i, _ip, _dp, _i, _vp, _i, _i, _i, _i, _i, _i, _d],
+    'ipa_warp_grid_plan': [_ip, _i, _i, _i, _vp, _vp, _vp, _ip, _ip],
     'ipa_conv2d_dev': [_vp, _vp, _i, _i, _i, _l, _dp, _i, _i, _vp, _l, _vp, _l, _i, _l, _l, _i,
                        _i, _d],
     'ipa_conv2d': [_vp, _vp, _i, _i, _i, _dp, _i, _i, _vp, _vp, _i, _i, _i, _d],

@@ -1,13 +1,16 @@
 """Perspective correction (homography warp) on MI355X behind the call surface of
 the reference's ``imgProcessor.camera.PerspectiveCorrection.PerspectiveCorrection``
 (reference: imgProcessor/camera/PerspectiveCorrection.py — __init__ :39-91,
-setReference :97-131, homography :133-191, uncorrect :374-378, correct :380-406,
-correctPoints :408-414).
+setReference :97-131, homography :133-191, correctGrid :281-372, uncorrect :374-378,
+correct :380-406, correctPoints :408-414).
 
 On the hot path: the warp itself (``correct`` = cv2.warpPerspective with
 INTER_LANCZOS4, ``uncorrect`` = INTER_CUBIC | WARP_INVERSE_MAP) runs as a HIP
 gather kernel that evaluates the homography per pixel in float64 — no map
-arrays, 8 B/px of HBM traffic for float32.
+arrays, 8 B/px of HBM traffic for float32.  ``correctGrid`` — one
+cv2.warpPerspective per lattice cell in the reference, 60 calls for a 6 x 10
+module — is ONE launch of the same kernel: every output pixel looks up the cell
+that owns it and evaluates that cell's homography (``ops.warp_grid``).
 
 Outside the accelerated path (raises NotImplementedError when requested):
 pose estimation (solvePnP), tilt-intensity correction, reference-image
@@ -111,6 +114,9 @@ class PerspectiveCorrection(object):
 
         def run(d):
             return ops.warp_perspective(d, M_dst2src, out_shape, interpolation, mode, val)
+        return self._on_device(img, run)
+
+    def _on_device(self, img, run):
         if isinstance(img, DeviceArray):
             return run(img)
         img = np.asarray(img)
@@ -127,6 +133,81 @@ class PerspectiveCorrection(object):
         sy, sx = self._size()
         Minv = np.linalg.inv(np.asarray(H, dtype=np.float64))
         return self._warp(img, Minv, (sy, sx), self.interpolation or 'lanczos4')
+
+    def _gridCells(self, grid):
+        """the cells of correctGrid in the reference's paint order (:317-371), host only:
+        -> (rects int32 (n, 4): x0, y0, w, h in the output; M float64 (n, 9): the cell's matrix from
+        its LOCAL destination pixel to the source, inv(getPerspectiveTransform(quad, objP)))"""
+        grid = np.asarray(grid)
+        if grid.ndim != 3 or grid.shape[2] != 2 or grid.shape[0] < 2 or grid.shape[1] < 2:
+            raise ValueError('grid must have shape (s0, s1, 2) with s0, s1 >= 2 (got %s)'
+                             % (grid.shape,))
+        n0, n1 = grid.shape[0] - 1, grid.shape[1] - 1
+        W, H = self._size()   # read as (width, height) here, see correctGrid
+        b = int(self.opts['border'])
+        sx, sy = (W - 2 * b) // n0, (H - 2 * b) // n1
+        if sx < 1 or sy < 1:
+            raise ValueError('new_size %s with border %d leaves no room for %d x %d cells'
+                             % ((W, H), b, n0, n1))
+        rects, mats = [], []
+
+        def cell(ix, iy, rows, cols, off):
+            # the view out[rows, cols], clipped as a numpy slice is; the matrix acts on its pixels
+            y0, y1, _ = slice(*rows).indices(H)
+            x0, x1, _ = slice(*cols).indices(W)
+            if y1 <= y0 or x1 <= x0:
+                return
+            quad = grid[ix:ix + 2, iy:iy + 2].reshape(4, 2)[[0, 2, 3, 1]].astype(np.float32)
+            objP = np.float32([[0, 0], [sx, 0], [sx, sy], [0, sy]]) + np.float32(off)
+            hcell = getPerspectiveTransform(quad, objP)
+            rects.append((x0, y0, x1 - x0, y1 - y0))
+            mats.append(np.linalg.inv(hcell).ravel())
+
+        xr = (n0 - 1) * sx + b
+        for ix in range(1, n0 - 1):                      # inner cells
+            for iy in range(1, n1 - 1):
+                cell(ix, iy, (iy * sy + b, (iy + 1) * sy + b), (ix * sx + b, (ix + 1) * sx + b), (0, 0))
+        for ix in range(1, n0 - 1):                      # top
+            cell(ix, 0, (None, sy + b), (ix * sx + b, (ix + 1) * sx + b), (0, b))
+        for ix in range(1, n0 - 1):                      # bottom
+            y, x = (n1 - 1) * sy + b, ix * sx + b
+            cell(ix, n1 - 1, (y, y + sy + b), (x, x + sx), (0, 0))
+        for iy in range(1, n1 - 1):                      # left
+            y = iy * sy + b
+            cell(0, iy, (y, y + sy), (None, sx + b), (b, 0))
+        for iy in range(1, n1 - 1):                      # right
+            y = iy * sy + b
+            cell(n0 - 1, iy, (y, y + sy), (xr, xr + sx + b), (0, 0))
+        # the corners; the -1 is the reference's (:361, :371): the two bottom ones start one row
+        # early, their content sits one row lower
+        cell(n0 - 1, n1 - 1, (-sy - b - 1, None), (xr, xr + sx + b), (0, 0))
+        cell(0, 0, (0, sy + b), (0, sx + b), (b, b))
+        cell(n0 - 1, 0, (None, sy + b), (xr, xr + sx + b), (0, b))
+        cell(0, n1 - 1, (-sy - b - 1, None), (None, sx + b), (b, 0))
+        return (np.array(rects, dtype=np.int32).reshape(-1, 4),
+                np.array(mats, dtype=np.float64).reshape(-1, 9))
+
+    def correctGrid(self, img, grid):
+        """rectify an object whose cell lattice is known - :281-372.  grid: (s0, s1, 2) source
+        points (x, y); every lattice cell is warped by its own homography into its own rectangle
+        of the output (cv2.warpPerspective(img, hcell, ..., flags=INTER_LANCZOS4) per cell in the
+        reference; here one launch, bit for bit the per-cell warps pasted in the same order).
+
+        As in the reference, new_size is read as (width, height) in THIS method and grid axis 0
+        runs along x: the output has shape new_size[::-1], the transpose of what correct()
+        returns for a non-square new_size.  The reference's off-by-one in the two bottom corner
+        cells is kept.  Pixels no cell covers (np.empty in the reference) receive the border
+        value.  No setReference() is needed: new_size is explicit.  The tilt-intensity division
+        is outside the accelerated path (do_correctIntensity raises in the constructor)."""
+        self.img = img
+        rects, M = self._gridCells(grid)
+        W, H = self._size()
+        mode, val = self._border_kw()
+        interpolation = self.interpolation or 'lanczos4'
+
+        def run(d):
+            return ops.warp_grid(d, rects, M, (H, W), interpolation, mode, val)
+        return self._on_device(img, run)
 
     def uncorrect(self, img):
         """inverse warp back into an image of img's own shape — :374-378

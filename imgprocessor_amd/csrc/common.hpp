@@ -147,6 +147,19 @@ struct ipa_ctx {
   size_t lens_map_bytes = 0;
   double lens_key[25];
   int lens_key_n = 0;
+  // the device tables of the last few piecewise warps (remap_grid.hip: cell records, band indices,
+  // owner matrix of one (cells, dh, dw)), keyed by content - the host copy of the call's arguments,
+  // compared with memcmp - and immutable once made; the least recently used one is replaced, after
+  // the stream has drained
+  static constexpr int kGridPlans = 4;
+  struct GridPlan {
+    std::vector<char> key;   // dh, dw, n_cells, the rectangles, the matrices
+    void* dev = nullptr;     // one allocation: cells | owner | colband | rowband
+    size_t off_owner = 0, off_col = 0, off_row = 0;
+    int n_colbands = 0;
+    unsigned long used = 0;
+  } grid_plans[kGridPlans];
+  unsigned long grid_plan_clock = 0;
   // No lock here: a context (stream + workspaces) belongs to ONE host thread at a time
   // (INTEGRATION.md section 4); the Python layer hands every thread its own default context.
 };

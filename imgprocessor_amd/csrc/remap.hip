@@ -8,6 +8,7 @@
 int ipa_remap_launch_map(ipa_ctx*, const RemapCall&, const MapCoord&, int map_vec);
 int ipa_remap_launch_undistort(ipa_ctx*, const RemapCall&, const UndistortCoord&);
 int ipa_remap_launch_homography(ipa_ctx*, const RemapCall&, const HomographyCoord&);
+int ipa_remap_launch_grid(ipa_ctx*, const RemapCall&, const int* cell_rects, const double* cell_M, int n_cells);
 int ipa_chain_one_kernel(const ipa_ctx* ctx, int src_dtype, int dst_dtype, int coord_kind, int interp);  // fused.hip: the remap alone as one kernel
 
 // ---------------------------------------------------------------- host side --
@@ -451,6 +452,19 @@ int ipa_warp_perspective_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
   return ipa_remap_launch_homography(ctx, a, c);
 }
 
+// PerspectiveCorrection.correctGrid (camera/PerspectiveCorrection.py:281-372): every cell's own
+// homography into its own rectangle, one launch (remap_grid.hip)
+int ipa_warp_grid_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, int sw, long src_pitch,
+                      const int* cell_rects, const double* cell_M, int n_cells, void* d_dst,
+                      int dst_dtype, int dh, int dw, long dst_pitch, int n_frames,
+                      long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
+                      double border_value) {
+  if (!ctx) return IPA_ERR_BAD_ARG;
+  RemapCall a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch,
+              n_frames, src_frame_stride, dst_frame_stride, interp, border_mode, border_value};
+  return ipa_remap_launch_grid(ctx, a, cell_rects, cell_M, n_cells);
+}
+
 int ipa_remap(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const float* mapx,
               const float* mapy, void* dst, int dst_dtype, int dh, int dw, int n_frames,
               int interp, int border_mode, double border_value) {
@@ -492,6 +506,21 @@ int ipa_warp_perspective(ipa_ctx* ctx, const void* src, int src_dtype, int sh, i
   rc = ipa_warp_perspective_dev(ctx, st.d_src, src_dtype, sh, sw, sw, M, st.d_dst, dst_dtype, dh,
                                 dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp,
                                 border_mode, border_value);
+  if (rc) return rc;
+  return stage_out(ctx, dst, st);
+}
+
+int ipa_warp_grid(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const int* cell_rects,
+                  const double* cell_M, int n_cells, void* dst, int dst_dtype, int dh, int dw,
+                  int n_frames, int interp, int border_mode, double border_value) {
+  if (!ctx) return IPA_ERR_BAD_ARG;
+  IPA_REQUIRE(ctx, dst, "null pointer");
+  Staged st;
+  int rc = stage_in(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
+  if (rc) return rc;
+  rc = ipa_warp_grid_dev(ctx, st.d_src, src_dtype, sh, sw, sw, cell_rects, cell_M, n_cells, st.d_dst,
+                         dst_dtype, dh, dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp,
+                         border_mode, border_value);
   if (rc) return rc;
   return stage_out(ctx, dst, st);
 }

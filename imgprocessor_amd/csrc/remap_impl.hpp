@@ -3,6 +3,7 @@
 //   ipa_remap*                 (cv2.remap,               LensDistortion.py:323-326)
 //   ipa_undistort*             (the two above fused: no map arrays in HBM)
 //   ipa_warp_perspective*      (cv2.warpPerspective,     PerspectiveCorrection.py:377-378,401-405)
+//   ipa_warp_grid*             (one warpPerspective per lattice cell, PerspectiveCorrection.py:281-372)
 //
 // Kernel shape: one wave64 owns 256 consecutive output pixels of one row
 // (4 px per lane -> 16-byte map loads and 16-byte stores, fully coalesced);
@@ -97,6 +98,21 @@ __device__ __forceinline__ void store4(DT* row, int x0, const DT (&v)[4], int n,
 #pragma unroll
     for (int k = 0; k < 4; k++)
       if (k < n) row[x0 + k] = v[k];
+  }
+}
+
+// The value remap_kernel<ST, DT, ., ., FIXED> stores for a sample wholly outside the source under
+// BORDER_CONSTANT: the border value as each of its arithmetic branches casts it.
+template <typename ST, typename DT, bool FIXED>
+__device__ __forceinline__ DT outside_value(double cval) {
+  if constexpr (std::is_integral<DT>::value && !FIXED) {
+    return store_cast<DT, double>(cval);
+  } else if constexpr (FIXED) {   // cv2's integer modes (uint8 -> uint8, uint16 -> uint16)
+    const double r = rint(cval), top = sizeof(DT) == 2 ? 65535.0 : 255.0;
+    return (DT)(r > 0 ? (r < top ? r : top) : 0);
+  } else {
+    using CT = typename compute_of<ST>::type;
+    return store_cast<DT, CT>((CT)cval);
   }
 }
 
@@ -251,6 +267,14 @@ __global__ void __launch_bounds__(256) remap_kernel(RemapParams p, Coord coord) 
 #pragma unroll
       for (int j = 0; j < BN; j++) out[b + j] = store_cast<DT, CT>(o[j]);
     }
+  }
+  if constexpr (coord_is_piecewise<Coord>::value) {
+    // pixels no piece covers: what a pixel wholly outside the source receives under
+    // BORDER_CONSTANT, whatever the call's border mode is
+    const DT hole = outside_value<ST, DT, FIXED>(p.cval);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (k < n && coord.cell_of(x0 + k, y) < 0) out[k] = hole;
   }
   DT* row = reinterpret_cast<DT*>(p.dst) + (long)frame * p.dst_frame_elems + (long)y * p.dpitch;
   store4<DT>(row, x0, out, n, p.dst_vec);
@@ -725,8 +749,12 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
     rc = ipa_u8_cubic_tab2d(ctx, &p.tab2d);
     if (rc) return rc;
   }
-  const bool u8_lz_tab = base == IPA_INTER_LANCZOS4 && a.src_dt == IPA_U8 && a.dst_dt == IPA_U8 &&
-                         ctx->tune.u8_lz_lds;
+  // a piecewise source (GridCoord) takes only the plain gather launch: the ring kernel, the
+  // stored-coordinates pass, the tile kernel and the uint8 Lanczos4 LDS kernel plan for one smooth
+  // coordinate field and have no hole rule - none of them is instantiated for it
+  constexpr bool kPiece = coord_is_piecewise<Coord>::value;
+  const bool u8_lz_tab = !kPiece && base == IPA_INTER_LANCZOS4 && a.src_dt == IPA_U8 &&
+                         a.dst_dt == IPA_U8 && ctx->tune.u8_lz_lds;
   if (u8_lz_tab) {
     rc = ipa_u8_lanczos_tab2d(ctx, &p.tab2d);
     if (rc) return rc;
@@ -828,28 +856,30 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
                         : base == IPA_INTER_LANCZOS4 ? (kMapSrc ? 3 : 2)
                                                      : (kMapSrc ? 8 : 4);
   const bool ring_pays = !(base == IPA_INTER_LINEAR && kHom) && a.n_frames >= ring_from;
-  if ((ctx->tune.ring_remap > 1 || (ctx->tune.ring_remap == 1 && ring_pays)) &&
-      a.n_frames >= ctx->tune.ring_min && a.src_dt == IPA_F32 && a.dst_dt == IPA_F32 &&
-      base != IPA_INTER_NEAREST) {
-    rc = ring_remap_launch<Coord>(ctx, p, coord, base, a.n_frames);
-    if (rc < 0) return rc;
-    if (p.skip) {
-      p.tiles = p.tiles_x * ((tiles_y + p.tile_rows - 1) / p.tile_rows);
-      grid = inner ? dim3(p.tiles * (unsigned)a.n_frames, 1) : dim3(p.tiles, (unsigned)a.n_frames);
+  if constexpr (!kPiece) {
+    if ((ctx->tune.ring_remap > 1 || (ctx->tune.ring_remap == 1 && ring_pays)) &&
+        a.n_frames >= ctx->tune.ring_min && a.src_dt == IPA_F32 && a.dst_dt == IPA_F32 &&
+        base != IPA_INTER_NEAREST) {
+      rc = ring_remap_launch<Coord>(ctx, p, coord, base, a.n_frames);
+      if (rc < 0) return rc;
+      if (p.skip) {
+        p.tiles = p.tiles_x * ((tiles_y + p.tile_rows - 1) / p.tile_rows);
+        grid = inner ? dim3(p.tiles * (unsigned)a.n_frames, 1) : dim3(p.tiles, (unsigned)a.n_frames);
+      }
+    }
+
+    if (u8_lz_tab) {
+      // 16 rows per pass and workgroup, 8 passes: 128 rows x 256 px per staging of the table
+      p.tile_rows = 8;
+      p.frames_inner = a.n_frames;
+      const unsigned bands = ((unsigned)a.dh + 16u * p.tile_rows - 1u) / (16u * p.tile_rows);
+      hipLaunchKernelGGL((remap_u8_lz_kernel<Coord>), dim3(p.tiles_x * bands * (unsigned)a.n_frames),
+                         dim3(1024), 0, ctx->stream, p, coord);
+      IPA_HIP(ctx, hipGetLastError());
+      return IPA_OK;
     }
   }
-
-  if (u8_lz_tab) {
-    // 16 rows per pass and workgroup, 8 passes: 128 rows x 256 px per staging of the table
-    p.tile_rows = 8;
-    p.frames_inner = a.n_frames;
-    const unsigned bands = ((unsigned)a.dh + 16u * p.tile_rows - 1u) / (16u * p.tile_rows);
-    hipLaunchKernelGGL((remap_u8_lz_kernel<Coord>), dim3(p.tiles_x * bands * (unsigned)a.n_frames),
-                       dim3(1024), 0, ctx->stream, p, coord);
-    IPA_HIP(ctx, hipGetLastError());
-    return IPA_OK;
-  }
-  if constexpr (!coord_is_table<Coord>::value) {
+  if constexpr (!coord_is_table<Coord>::value && !kPiece) {
     const int smin = ctx->tune.stored_coords;
     if (!p.skip && smin > 0 && a.n_frames >= smin && a.src_dt == IPA_F32 && a.dst_dt == IPA_F32 &&
         (base == IPA_INTER_CUBIC_CV || base == IPA_INTER_CUBIC_KEYS || base == IPA_INTER_LANCZOS4)) {
@@ -866,8 +896,14 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
     }
   }
   int s = a.src_dt, d = a.dst_dt;
-  if (p.skip) {
-    launch_rest<Coord>(ctx, p, coord, base, grid);
+  bool rest = false;
+  if constexpr (!kPiece) {
+    if (p.skip) {
+      launch_rest<Coord>(ctx, p, coord, base, grid);
+      rest = true;
+    }
+  }
+  if (rest) {
   } else if (s == IPA_F32 && d == IPA_F32) {
     launch_interp<float, float, Coord, false>(ctx, p, coord, base, grid);
   } else if (s == IPA_F64 && d == IPA_F64) {

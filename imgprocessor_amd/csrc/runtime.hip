@@ -202,6 +202,8 @@ int ipa_ctx_destroy(ipa_ctx* c) {
   if (c->tab) (void)hipFree(c->tab);
   if (c->plan) (void)hipFree(c->plan);
   if (c->lens_map) (void)hipFree(c->lens_map);
+  for (auto& gp : c->grid_plans)
+    if (gp.dev) (void)hipFree(gp.dev);
   for (auto& hnt : c->tile_slow)
     if (hnt.copied) (void)hipEventDestroy(hnt.copied);
   if (c->tile_slow_dev) (void)hipFree(c->tile_slow_dev);

@@ -1135,4 +1135,52 @@ struct HomographyCoord {
   }
 };
 
+// PerspectiveCorrection.correctGrid (camera/PerspectiveCorrection.py:281-372): one homography per
+// lattice cell, each painting its own rectangle of the output - the reference's sequence of
+// cv2.warpPerspective calls into views of one array, as ONE coordinate field.  The output is cut
+// at every rectangle edge into column and row bands; owner[row band][column band] is the LAST
+// rectangle of the paint order that covers the band pair (-1: none, a hole).  A cell's matrix maps
+// its LOCAL destination pixel (X - x0, Y - y0) to the source and is evaluated on those integers
+// exactly as HomographyCoord::get does: the bits of a per-cell ipa_warp_perspective_dev call.
+// The tables are a plan of remap_grid.hip (device memory, immutable once made).
+struct GridCell {
+  double m[9];
+  int x0, y0;
+};
+struct GridCoord {
+  using coord_t = double;
+  const GridCell* cells;
+  const uint16_t* colband;   // [dw]
+  const uint16_t* rowband;   // [dh]
+  const int16_t* owner;      // [n_rowbands][n_colbands]
+  int n_colbands;
+  __device__ __forceinline__ int cell_of(int X, int Y) const {
+    return owner[(int)rowband[Y] * n_colbands + (int)colband[X]];
+  }
+  // a hole samples (0, 0), harmlessly: remap_kernel overwrites it with the hole value
+  __device__ __forceinline__ void get(int X, int Y, double& sx, double& sy) const {
+#pragma clang fp contract(off)
+    sx = 0.0;
+    sy = 0.0;
+    const int c = cell_of(X, Y);
+    if (c < 0) return;
+    const GridCell& g = cells[c];
+    double du = (double)(X - g.x0), dv = (double)(Y - g.y0);
+    double Xs = g.m[0] * du + g.m[1] * dv + g.m[2];
+    double Ys = g.m[3] * du + g.m[4] * dv + g.m[5];
+    double W = g.m[6] * du + g.m[7] * dv + g.m[8];
+    if (W != 0.0) {
+      double iw = 1.0 / W;
+      sx = Xs * iw;
+      sy = Ys * iw;
+    }
+  }
+};
+// a coordinate source made of pieces: no single smooth field (the ring kernel's strip plans, the
+// stored-coordinates pass, the tile kernel's boxes and the uint8 Lanczos4 LDS kernel assume one)
+// and pixels that belong to no piece.  Such a source takes only the plain gather launch, and
+// remap_kernel gives its holes the value BORDER_CONSTANT gives a pixel wholly outside the source.
+template <typename Coord> struct coord_is_piecewise : std::false_type {};
+template <> struct coord_is_piecewise<GridCoord> : std::true_type {};
+
 }  // namespace ipa

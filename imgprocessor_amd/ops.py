@@ -241,6 +241,69 @@ def warp_perspective(src, M_dst2src, out_shape, interpolation='linear', border_m
     return dst
 
 
+def _grid_cells(cell_rects, cell_M):
+    rects = np.ascontiguousarray(cell_rects, dtype=np.int32)
+    M = np.ascontiguousarray(cell_M, dtype=np.float64)
+    if rects.ndim != 2 or rects.shape[1] != 4:
+        raise ValueError('cell_rects must have shape (n, 4): x0, y0, w, h (got %s)' % (rects.shape,))
+    n = rects.shape[0]
+    if M.size != 9 * n or M.shape[0] != n:
+        raise ValueError('cell_M must hold one 3x3 matrix per cell (got %s for %d cells)'
+                         % (M.shape, n))
+    return rects, M, n
+
+
+def warp_grid_plan(cell_rects, out_shape):
+    """who owns which pixel of a piecewise warp (ipa_warp_grid_plan; host only, no device):
+    -> (colband (dw,) uint16, rowband (dh,) uint16, owner (n_rowbands, n_colbands) int16), the
+    pixel (x, y) belongs to cell owner[rowband[y], colband[x]], -1 = none"""
+    rects = np.ascontiguousarray(cell_rects, dtype=np.int32).reshape(-1, 4)
+    dh, dw = int(out_shape[0]), int(out_shape[1])
+    lib = L.lib()
+    nr, nc = C.c_int(0), C.c_int(0)
+    rp = rects.ctypes.data_as(L._ip)
+    L.check(lib.ipa_warp_grid_plan(rp, rects.shape[0], dh, dw, None, None, None, C.byref(nr),
+                                   C.byref(nc)), None, 'warp_grid_plan')
+    col, row = np.empty(dw, np.uint16), np.empty(dh, np.uint16)
+    owner = np.empty((nr.value, nc.value), np.int16)
+    L.check(lib.ipa_warp_grid_plan(rp, rects.shape[0], dh, dw, _p(col), _p(row), _p(owner),
+                                   C.byref(nr), C.byref(nc)), None, 'warp_grid_plan')
+    return col, row, owner
+
+
+def warp_grid(src, cell_rects, cell_M, out_shape, interpolation='linear', border_mode='constant',
+              border_value=0.0, out_dtype=None, out=None, ctx=None):
+    """piecewise cv2.warpPerspective in one launch (PerspectiveCorrection.correctGrid): cell i
+    paints the rectangle cell_rects[i] = (x0, y0, w, h) of the output through cell_M[i], the 3x3
+    matrix from the cell's LOCAL destination pixel (X - x0, Y - y0, 1) to the source - bit for bit
+    ``warp_perspective(src, cell_M[i], (h, w), ...)`` pasted there.  Rectangles come in paint
+    order; where they overlap the last one wins.  Pixels no rectangle covers receive what a
+    pixel wholly outside the source receives under 'constant' with border_value."""
+    interp, border = interp_id(interpolation), border_id(border_mode)
+    rects, M, nc = _grid_cells(cell_rects, cell_M)
+    rp, mp = rects.ctypes.data_as(L._ip), M.ctypes.data_as(L._dp)
+    dev = _is_dev(src)
+    ctx = _ctx_of(src, ctx=ctx)
+    if not dev:
+        src = _host(src)
+    n, sh, sw = as_frames(src)
+    dh, dw = int(out_shape[0]), int(out_shape[1])
+    odt = _out_dtype(src.dtype, out_dtype)
+    oshape = (dh, dw) if len(src.shape) == 2 else (n, dh, dw)
+    if dev:
+        dst = _dev_out(ctx, out, oshape, odt)
+        ctx._check(ctx._lib.ipa_warp_grid_dev(ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
+                                              rp, mp, nc, dst.ptr, dtype_id(odt), dh, dw, dw, n,
+                                              sh * sw, dh * dw, interp, border,
+                                              float(border_value)), 'warp_grid')
+        return dst
+    dst = np.empty(oshape, odt)
+    ctx._check(ctx._lib.ipa_warp_grid(ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, rp, mp, nc,
+                                      _p(dst), dtype_id(odt), dh, dw, n, interp, border,
+                                      float(border_value)), 'warp_grid')
+    return dst
+
+
 # --------------------------------------------------------------- filters --
 def _float_img(img):
     """filters run on float32/float64 (the reference's toFloatArray rule for ints)"""

@@ -184,6 +184,33 @@ int ipa_warp_perspective(ipa_ctx* ctx, const void* src, int src_dtype, int sh, i
                          const double* M, void* dst, int dst_dtype, int dh, int dw, int n_frames,
                          int interp, int border_mode, double border_value);
 
+/* replaces the per-cell cv2.warpPerspective calls of PerspectiveCorrection.correctGrid
+ * (camera/PerspectiveCorrection.py:281-372) with ONE launch: n_cells cells, each with a
+ * destination rectangle cell_rects[i] = {x0, y0, w, h} and a 3x3 row-major double matrix
+ * cell_M[9 i ..] that maps the cell's LOCAL destination pixel (X - x0, Y - y0, 1) to source
+ * coordinates (both HOST pointers).  Rectangles come in paint order and may overlap: the last one
+ * that covers a pixel owns it.  Every pixel is bit for bit what ipa_warp_perspective_dev gives for
+ * its cell (same dtypes, interpolations and border modes).  A pixel no rectangle covers receives
+ * what a pixel wholly outside the source receives under IPA_BORDER_CONSTANT with border_value,
+ * whatever border_mode is.  IPA_ERR_BAD_ARG: n_cells outside [1, 32767], a rectangle that is
+ * empty or not inside the destination, more than 65535 bands on an axis. */
+int ipa_warp_grid_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, int sw, long src_pitch,
+                      const int* cell_rects, const double* cell_M, int n_cells, void* d_dst,
+                      int dst_dtype, int dh, int dw, long dst_pitch, int n_frames,
+                      long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
+                      double border_value);
+int ipa_warp_grid(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const int* cell_rects,
+                  const double* cell_M, int n_cells, void* dst, int dst_dtype, int dh, int dw,
+                  int n_frames, int interp, int border_mode, double border_value);
+/* The ownership resolution behind ipa_warp_grid_dev as a pure host function (no context, no
+ * device; the device entry calls it): the destination cut at every rectangle edge into column
+ * and row bands.  colband[dw] / rowband[dh]: the band of a column / row; owner[n_rowbands *
+ * n_colbands], row-major: the last cell that covers the band pair, -1 = none.  Each of the three
+ * may be NULL (a first call for the band counts sizes `owner`).  The pixel (x, y) belongs to
+ * owner[rowband[y] * n_colbands + colband[x]].  Errors as above (ipa_last_error(NULL)). */
+int ipa_warp_grid_plan(const int* cell_rects, int n_cells, int dh, int dw, uint16_t* colband,
+                       uint16_t* rowband, int16_t* owner, int* n_rowbands, int* n_colbands);
+
 /* ---------------------------------------------------------------- filters */
 /* dense kh x kw centred correlation (== scipy.ndimage.correlate, origin 0):
  *   dst[y,x] = sum_{i,j} kernel[i,j] * src[y+i-kh/2, x+j-kw/2]
