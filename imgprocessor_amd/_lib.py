@@ -21,6 +21,9 @@ BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT10
  STENCIL_CLOSEST_DISTANCE, STENCIL_POS_INTENSITY_UNC, STENCIL_MEDIAN_THRESHOLD,
  STENCIL_VAR_Y_GAUSS, STENCIL_CONV_YDEP) = range(9)
 
+# ipa_cv_table_id of ipa_cv_table
+CV_TABLE_ROWS, CV_TABLE_U8_CUBIC, CV_TABLE_U8_LANCZOS4 = range(3)
+
 # ipa_conv_op of ipa_conv_path
 CONV_CONV2D, CONV_SEPCONV2D, CONV_SEPCONV2D_LDS = range(3)
 
@@ -66,6 +69,7 @@ PROTOTYPES = {
     'ipa_remap_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _vp, _l, _vp, _i, _i, _i, _l, _i, _l, _l,
                       _i, _i, _d],
     'ipa_remap': [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d],
+    'ipa_cv_table': [_i, _vp, _sz],
     'ipa_undistort_dev': [_vp, _vp, _i, _i, _i, _l, _dp, _dp, _dp, _vp, _i, _i, _i, _l, _i, _l,
                           _l, _i, _i, _d],
     'ipa_undistort': [_vp, _vp, _i, _i, _i, _dp, _dp, _dp, _vp, _i, _i, _i, _i, _i, _i, _d],

@@ -3,9 +3,11 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <initializer_list>
 #include <vector>
 
 #include <mutex>
@@ -169,19 +171,32 @@ struct ipa_event {
 };
 
 void ipa_set_error(ipa_ctx* ctx, const char* fmt, ...);
-int ipa_ws_reserve(ipa_ctx* ctx, size_t bytes);                         // ctx->ws >= bytes
-// the host-pointer fills (idw.hip, interp_more.hip): grid and mask (never null: the callers refuse
-// that, each in its own words) staged through ctx->ws; then the grid copied back and the stream drained
-int ipa_fill_stage(ipa_ctx* ctx, const void* grid, int dtype, const uint8_t* mask, int h, int w,
-                   char** d_grid, uint8_t** d_mask, size_t* grid_bytes);
-int ipa_fill_back(ipa_ctx* ctx, void* grid, const char* d_grid, size_t grid_bytes);
+// grow-only device buffers of a context (runtime.hip): *buf holds >= bytes afterwards.  When it has to grow, the
+// stream is drained, the old buffer freed and `want` (>= bytes: the caller's slack) allocated.
+int ipa_grow_reserve(ipa_ctx* ctx, void** buf, size_t* have, size_t bytes, size_t want);
+int ipa_ws_reserve(ipa_ctx* ctx, size_t bytes);                         // ctx->ws >= bytes (+25 % + 1 MiB)
+// The host-pointer entry points: their arrays staged through ctx->ws.  ipa_stage_in selects the context's device,
+// reserves the workspace once for all slots - in the order given, each on a 256-byte boundary -, uploads the slots that
+// have a host source and hands back the device pointers (d[i]; null for a slot of 0 bytes).  ipa_stage_out copies the
+// named slots back and drains the stream.
+struct ipa_stage_slot {
+  const void* host;   // null: nothing to upload (a result, or scratch)
+  size_t bytes;
+};
+struct ipa_stage_back {
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+int ipa_stage_in(ipa_ctx* ctx, std::initializer_list<ipa_stage_slot> slots, char** d);
+int ipa_stage_out(ipa_ctx* ctx, std::initializer_list<ipa_stage_back> backs);
 int ipa_lens_map_cached(ipa_ctx* ctx, const double* K, const double* dist5, const double* newK,
                         int h, int w, float** mx, float** my);
 // remap.hip -> fused.hip: the strip remap of integer frames into their own type (1: not a call it covers)
 int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int sw, long src_pitch, const float* d_mapx,
                         const float* d_mapy, long map_pitch, void* d_dst, int dh, int dw, long dst_pitch, int n_frames,
                         long src_frame_stride, long dst_frame_stride, int interp, int border_mode, double border_value);
-int ipa_plan_reserve(ipa_ctx* ctx, size_t bytes);                       // ctx->plan >= bytes
+int ipa_plan_reserve(ipa_ctx* ctx, size_t bytes);                       // ctx->plan >= bytes (+50 % + 64 KiB); forgets plan_key
 int ipa_tab_upload(ipa_ctx* ctx, const void* host, size_t bytes, void** d);  // stream-ordered
 
 #define IPA_HIP(ctx, call)                                                            \
@@ -240,6 +255,42 @@ static inline size_t ipa_dtype_size(int dt) {
     case IPA_F64: return 8;
   }
   return 0;
+}
+
+// Do the rows of an image (and, of a batch, its frames) start on multiples of vec_bytes?
+static inline bool aligned_rows(const void* base, long pitch_elems, long frame_elems, int n_frames,
+                                size_t elem, size_t vec_bytes) {
+  if (((uintptr_t)base) % vec_bytes) return false;
+  if ((pitch_elems * (long)elem) % (long)vec_bytes) return false;
+  if (n_frames > 1 && (frame_elems * (long)elem) % (long)vec_bytes) return false;
+  return true;
+}
+
+// How far the source row of homography m moves along one output row (px per px), the largest of 9 points of the
+// dh x dw picture; 1e6 where it is not finite (no caller's threshold is near).
+static inline double homography_row_drift(const double* m, int dh, int dw) {
+  double drift = 0;
+  for (int py = 0; py < 3; py++)
+    for (int px = 0; px < 3; px++) {
+      const double u = (dw - 2) * 0.5 * px, v = (dh - 2) * 0.5 * py;
+      double y[2];
+      for (int i = 0; i < 2; i++) {
+        const double W = m[6] * (u + i) + m[7] * v + m[8];
+        y[i] = (m[3] * (u + i) + m[4] * v + m[5]) * (W != 0.0 ? 1.0 / W : 0.0);
+      }
+      if (!(fabs(y[1] - y[0]) < 1e6)) return 1e6;
+      drift = fabs(y[1] - y[0]) > drift ? fabs(y[1] - y[0]) : drift;
+    }
+  return drift;
+}
+
+// the argument checks the host-pointer fills share (idw.hip, interp_more.hip); *grid_bytes = the h x w grid
+static inline int ipa_fill_args(ipa_ctx* ctx, const void* grid, int dtype, int h, int w, size_t* grid_bytes) {
+  IPA_REQUIRE(ctx, grid && h > 0 && w > 0, "bad arguments");
+  const size_t es = ipa_dtype_size(dtype);
+  IPA_REQUIRE(ctx, es, "unknown dtype");
+  *grid_bytes = (size_t)h * w * es;
+  return IPA_OK;
 }
 
 // -------------------------------------------------------------------------

@@ -340,13 +340,6 @@ extend_kernel(const T* __restrict__ src, int h, int w, long spitch, int px, int 
 
 using namespace ipa;
 
-static bool rows_aligned16(const void* base, long pitch, long frame, int n_frames, size_t es) {
-  if (((uintptr_t)base) & (IPA_VEC_ALIGN - 1)) return false;
-  if ((pitch * (long)es) & (IPA_VEC_ALIGN - 1)) return false;
-  if (n_frames > 1 && ((frame * (long)es) & (IPA_VEC_ALIGN - 1))) return false;
-  return true;
-}
-
 template <typename T, int K>
 static void launch_conv(ipa_ctx* ctx, const ConvParams& p, const double* kernel, int n_frames) {
   Weights<T, K * K> w;
@@ -510,8 +503,8 @@ int ipa_conv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, lon
   p.bx = border_x; p.by = border_y; p.cval = border_value;
   p.tiles_x = (unsigned)((w + kTileW - 1) / kTileW);
   p.tiles = p.tiles_x * (unsigned)((h + kTileH - 1) / kTileH);
-  p.vec_in = rows_aligned16(d_src, src_pitch, src_frame_stride, n_frames, es);
-  p.vec_out = rows_aligned16(d_dst, dst_pitch, dst_frame_stride, n_frames, es);
+  p.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
+  p.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   if (dtype == IPA_F32) return conv_typed<float>(ctx, p, kernel, kh, kw, n_frames);
   return conv_typed<double>(ctx, p, kernel, kh, kw, n_frames);
@@ -571,10 +564,10 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
     wp.dst = (char*)d_dst; wp.dst_frame_elems = dst_frame_stride;
     wp.dh = h; wp.dw = w; wp.dpitch = dst_pitch;
     wp.cbx = border_x; wp.cby = border_y;
-    wp.vec_out = rows_aligned16(d_dst, dst_pitch, dst_frame_stride, n_frames, es);
+    wp.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
     LoadRowSrc src;
     src.base = (const float*)d_src; src.frame_elems = src_frame_stride; src.pitch = src_pitch;
-    src.vec_in = rows_aligned16(d_src, src_pitch, src_frame_stride, n_frames, es);
+    src.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
     src.cval = (float)border_value;
     IPA_HIP(ctx, hipSetDevice(ctx->device));
     if (ipa_wave_sep_launch(ctx, wp, src, ky, nky, kx, nkx, n_frames, (float)border_value) == 0) {
@@ -591,8 +584,8 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   p.tiles = p.tiles_x * (unsigned)((h + kTileH - 1) / kTileH);
   p.nky = nky; p.nkx = nkx; p.hy = nky / 2; p.hx = nkx / 2;
   p.hxa = ((p.hx + 3) / 4) * 4;
-  p.vec_in = rows_aligned16(d_src, src_pitch, src_frame_stride, n_frames, es);
-  p.vec_out = rows_aligned16(d_dst, dst_pitch, dst_frame_stride, n_frames, es);
+  p.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
+  p.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
   size_t lds = sepconv_lds(es, nky, nkx);
   IPA_REQUIRE(ctx, lds <= 160 * 1024, "separable kernel too large for LDS");
   dim3 grid(p.tiles, (unsigned)n_frames), block(32, 8);
@@ -689,21 +682,14 @@ int ipa_conv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const dou
   IPA_REQUIRE(ctx, src && dst && h > 0 && w > 0 && n_frames >= 1, "bad arguments");
   size_t es = ipa_dtype_size(dtype);
   IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t ib = (size_t)h * w * es * n_frames, mb = mask ? (size_t)h * w : 0;
-  int rc = ipa_ws_reserve(ctx, 2 * up(ib) + up(mb));
+  const size_t ib = (size_t)h * w * es * n_frames, mb = mask ? (size_t)h * w : 0;
+  char* d[3];   // in, out, mask (null without one)
+  int rc = ipa_stage_in(ctx, {{src, ib}, {nullptr, ib}, {mask, mb}}, d);
   if (rc) return rc;
-  char* d_in = (char*)ctx->ws;
-  char* d_out = d_in + up(ib);
-  uint8_t* d_m = mask ? (uint8_t*)(d_out + up(ib)) : nullptr;
-  IPA_HIP(ctx, hipMemcpyAsync(d_in, src, ib, hipMemcpyHostToDevice, ctx->stream));
-  if (mask) IPA_HIP(ctx, hipMemcpyAsync(d_m, mask, mb, hipMemcpyHostToDevice, ctx->stream));
-  rc = ipa_conv2d_dev(ctx, d_in, dtype, h, w, w, kernel, kh, kw, d_m, w, d_out, w, n_frames,
+  rc = ipa_conv2d_dev(ctx, d[0], dtype, h, w, w, kernel, kh, kw, (const uint8_t*)d[2], w, d[1], w, n_frames,
                       (long)h * w, (long)h * w, border_x, border_y, border_value);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(dst, d_out, ib, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{dst, d[1], ib}});
 }
 
 int ipa_sepconv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const double* ky,
@@ -713,19 +699,14 @@ int ipa_sepconv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const 
   IPA_REQUIRE(ctx, src && dst && h > 0 && w > 0 && n_frames >= 1, "bad arguments");
   size_t es = ipa_dtype_size(dtype);
   IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t ib = (size_t)h * w * es * n_frames;
-  int rc = ipa_ws_reserve(ctx, 2 * up(ib));
+  const size_t ib = (size_t)h * w * es * n_frames;
+  char* d[2];   // in, out
+  int rc = ipa_stage_in(ctx, {{src, ib}, {nullptr, ib}}, d);
   if (rc) return rc;
-  char* d_in = (char*)ctx->ws;
-  char* d_out = d_in + up(ib);
-  IPA_HIP(ctx, hipMemcpyAsync(d_in, src, ib, hipMemcpyHostToDevice, ctx->stream));
-  rc = ipa_sepconv2d_dev(ctx, d_in, dtype, h, w, w, ky, nky, kx, nkx, d_out, w, n_frames,
+  rc = ipa_sepconv2d_dev(ctx, d[0], dtype, h, w, w, ky, nky, kx, nkx, d[1], w, n_frames,
                          (long)h * w, (long)h * w, border_y, border_x, border_value);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(dst, d_out, ib, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{dst, d[1], ib}});
 }
 
 }  // extern "C"

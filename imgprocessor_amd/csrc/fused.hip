@@ -148,8 +148,7 @@ static int fused_fill(ipa_ctx* ctx, FusedCall& f, const ChainArgs& a) {
   p.dst_frame_elems = a.dst_frame_stride;
   p.dh = a.dh; p.dw = a.dw; p.dpitch = a.dst_pitch;
   p.cbx = a.conv_border_x; p.cby = a.conv_border_y;
-  p.vec_out = (((uintptr_t)a.dst) % IPA_VEC_ALIGN == 0) && ((a.dst_pitch * (long)ds) % IPA_VEC_ALIGN == 0) &&
-              (a.n_frames == 1 || (a.dst_frame_stride * (long)ds) % IPA_VEC_ALIGN == 0);
+  p.vec_out = aligned_rows(a.dst, a.dst_pitch, a.dst_frame_stride, a.n_frames, ds, IPA_VEC_ALIGN);
   f.src = (const char*)a.src;
   f.src_frame_bytes = a.src_frame_stride * (long)ss;
   f.src_bytes = (unsigned)frame_bytes;
@@ -158,11 +157,8 @@ static int fused_fill(ipa_ctx* ctx, FusedCall& f, const ChainArgs& a) {
   f.cubic_a = base == IPA_INTER_CUBIC_KEYS ? -0.5f : -0.75f;
   f.cval = a.border_value;
   f.conv_cval = 0.0;
-  if (f.coord_kind == 0)
-    f.map_vec = (((uintptr_t)f.map.mx) % IPA_VEC_ALIGN == 0) && (((uintptr_t)f.map.my) % IPA_VEC_ALIGN == 0) &&
-                ((f.map.pitch * 4) % IPA_VEC_ALIGN == 0);
-  else
-    f.map_vec = 0;
+  f.map_vec = f.coord_kind == 0 && aligned_rows(f.map.mx, f.map.pitch, 0, 1, 4, IPA_VEC_ALIGN) &&
+              aligned_rows(f.map.my, f.map.pitch, 0, 1, 4, IPA_VEC_ALIGN);
   f.src_dt = a.src_dtype; f.dst_dt = a.dst_dtype; f.interp_base = base; f.n_frames = a.n_frames;
   f.kernel = nullptr;
   return IPA_OK;
@@ -244,22 +240,8 @@ static bool rotated_warp_in_two_launches(const ipa_ctx* ctx, const double* m, in
   if (!ctx->tune.tile_warp || src_dtype != IPA_F32 || dst_dtype != IPA_F32) return false;
   if ((interp & 0xff) != IPA_INTER_LINEAR) return false;
   if (n_frames < 8 || (double)n_frames * dh * dw < 64e6) return false;
-  auto at = [&](double u, double v, double& sx, double& sy) {
-    const double W = m[6] * u + m[7] * v + m[8], iw = W != 0.0 ? 1.0 / W : 0.0;
-    sx = (m[0] * u + m[1] * v + m[2]) * iw;
-    sy = (m[3] * u + m[4] * v + m[5]) * iw;
-  };
-  double drift = 0;
-  for (int py = 0; py < 3; py++)
-    for (int px = 0; px < 3; px++) {
-      const double u = (dw - 2) * 0.5 * px, v = (dh - 2) * 0.5 * py;
-      double x0, y0, x1, y1;
-      at(u, v, x0, y0);
-      at(u + 1, v, x1, y1);
-      if (!(fabs(y1 - y0) < 1e6)) return false;
-      drift = fabs(y1 - y0) > drift ? fabs(y1 - y0) : drift;
-    }
-  return drift >= (ctx->tune.tile_warp > 1 ? 0.0 : 0.2);
+  const double drift = homography_row_drift(m, dh, dw);
+  return drift < 1e6 && drift >= (ctx->tune.tile_warp > 1 ? 0.0 : 0.2);   // (not finite: never)
 }
 
 // The lens model through its cached float32 map (knob lens_cache): the model's coordinates are the same for every frame

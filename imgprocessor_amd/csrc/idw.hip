@@ -210,24 +210,28 @@ int ipa_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h
                  int ksize, const double* weights) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "bad arguments");
-  char* dg; uint8_t* dm; size_t gb;
-  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, weights);
+  char* d[2];   // grid, mask
+  if ((rc = ipa_stage_in(ctx, {{grid, gb}, {mask, (size_t)h * w}}, d))) return rc;
+  rc = ipa_idw_fill_dev(ctx, d[0], dtype, (uint8_t*)d[1], h, w, w, ksize, weights);
   if (rc) return rc;
-  return ipa_fill_back(ctx, grid, dg, gb);
+  return ipa_stage_out(ctx, {{grid, d[0], gb}});
 }
 
 int ipa_fast_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
                       const int32_t* offsets, const double* weights, int n, int minnvals) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "bad arguments");
-  char* dg; uint8_t* dm; size_t gb;
-  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_fast_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, offsets, weights, n, minnvals);
+  char* d[2];   // grid, mask
+  if ((rc = ipa_stage_in(ctx, {{grid, gb}, {mask, (size_t)h * w}}, d))) return rc;
+  rc = ipa_fast_idw_fill_dev(ctx, d[0], dtype, (uint8_t*)d[1], h, w, w, offsets, weights, n, minnvals);
   if (rc) return rc;
-  return ipa_fill_back(ctx, grid, dg, gb);
+  return ipa_stage_out(ctx, {{grid, d[0], gb}});
 }
 
 }  // extern "C"

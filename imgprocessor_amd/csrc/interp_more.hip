@@ -546,44 +546,46 @@ int ipa_cross_avg_fill_dev(ipa_ctx* ctx, void* d_grid, int dtype, const uint8_t*
   });
 }
 
-// host-pointer forms: grid (and mask) staged through the context's workspace
-// (ipa_fill_stage / ipa_fill_back, runtime.hip)
+// host-pointer forms: grid (and mask) staged through the context's workspace (ipa_stage_in / ipa_stage_out)
 int ipa_unstructured_idw(ipa_ctx* ctx, void* grid, int dtype, int h, int w, const double* x,
                          const double* y, const double* v, int n, double power) {
   if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, grid && h > 0 && w > 0, "bad arguments");
-  const size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  const size_t gb = (size_t)h * w * es;
-  int rc = ipa_ws_reserve(ctx, gb);  // every pixel is written: nothing to upload
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_unstructured_idw_dev(ctx, ctx->ws, dtype, h, w, w, x, y, v, n, power);
+  char* d;
+  if ((rc = ipa_stage_in(ctx, {{nullptr, gb}}, &d))) return rc;  // every pixel is written: nothing to upload
+  rc = ipa_unstructured_idw_dev(ctx, d, dtype, h, w, w, x, y, v, n, power);
   if (rc) return rc;
-  return ipa_fill_back(ctx, grid, (const char*)ctx->ws, gb);
+  return ipa_stage_out(ctx, {{grid, d, gb}});
 }
 
 int ipa_circular_idw_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
                           int ksize, double power, double fr, double fphi, double cx, double cy) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
-  char* dg; uint8_t* dm; size_t gb;
-  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_circular_idw_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, power, fr, fphi, cx, cy);
+  char* d[2];   // grid, mask
+  if ((rc = ipa_stage_in(ctx, {{grid, gb}, {mask, (size_t)h * w}}, d))) return rc;
+  rc = ipa_circular_idw_fill_dev(ctx, d[0], dtype, (uint8_t*)d[1], h, w, w, ksize, power, fr, fphi, cx, cy);
   if (rc) return rc;
-  return ipa_fill_back(ctx, grid, dg, gb);
+  return ipa_stage_out(ctx, {{grid, d[0], gb}});
 }
 
 int ipa_cross_avg_fill(ipa_ctx* ctx, void* grid, int dtype, const uint8_t* mask, int h, int w,
                        int ksize, double power) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
-  char* dg; uint8_t* dm; size_t gb;
-  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_cross_avg_fill_dev(ctx, dg, dtype, dm, h, w, w, ksize, power);
+  char* d[2];   // grid, mask
+  if ((rc = ipa_stage_in(ctx, {{grid, gb}, {mask, (size_t)h * w}}, d))) return rc;
+  rc = ipa_cross_avg_fill_dev(ctx, d[0], dtype, (uint8_t*)d[1], h, w, w, ksize, power);
   if (rc) return rc;
-  return ipa_fill_back(ctx, grid, dg, gb);
+  return ipa_stage_out(ctx, {{grid, d[0], gb}});
 }
 
 int ipa_point_spread_idw_dev(ipa_ctx* ctx, void* d_grid, int dtype, uint8_t* d_mask, int h, int w,
@@ -631,14 +633,15 @@ int ipa_point_spread_idw(ipa_ctx* ctx, void* grid, int dtype, uint8_t* mask, int
                          int ksize, double power, long max_iter) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mask, "null mask");
-  char* dg; uint8_t* dm; size_t gb;
-  int rc = ipa_fill_stage(ctx, grid, dtype, mask, h, w, &dg, &dm, &gb);
+  size_t gb;
+  int rc = ipa_fill_args(ctx, grid, dtype, h, w, &gb);
   if (rc) return rc;
-  rc = ipa_point_spread_idw_dev(ctx, dg, dtype, dm, h, w, w, ksize, power, max_iter);
+  char* d[2];   // grid, mask
+  if ((rc = ipa_stage_in(ctx, {{grid, gb}, {mask, (size_t)h * w}}, d))) return rc;
+  rc = ipa_point_spread_idw_dev(ctx, d[0], dtype, (uint8_t*)d[1], h, w, w, ksize, power, max_iter);
   if (rc) return rc;
   // the mask is modified too (filled pixels are unmasked)
-  IPA_HIP(ctx, hipMemcpyAsync(mask, dm, (size_t)h * w, hipMemcpyDeviceToHost, ctx->stream));
-  return ipa_fill_back(ctx, grid, dg, gb);
+  return ipa_stage_out(ctx, {{mask, d[1], (size_t)h * w}, {grid, d[0], gb}});
 }
 
 // the constants and predicates of this file and of resize.hip: interp_paths.hpp

@@ -4,6 +4,7 @@
 
 #define IPA_REMAP_API_TU
 #include "remap_impl.hpp"
+#include "cv_tables.hpp"
 
 int ipa_remap_launch_map(ipa_ctx*, const RemapCall&, const MapCoord&, int map_vec);
 int ipa_remap_launch_undistort(ipa_ctx*, const RemapCall&, const UndistortCoord&);
@@ -34,171 +35,33 @@ int make_undistort_coord(ipa_ctx* ctx, const double* K, const double* d, const d
   return IPA_OK;
 }
 
-// OpenCV interpolateLanczos4 evaluated at k/32, k = 0..31 (the rows of cv2's
-// Lanczos4 interpolation table)
-static void lanczos4_row(float x, float* coeffs) {
-  static const double s45 = 0.70710678118654752440084436210485;
-  static const double cs[][2] = {{1, 0},  {-s45, -s45}, {0, 1},  {s45, -s45},
-                                 {-1, 0}, {s45, s45},   {0, -1}, {-s45, s45}};
-  if (x < 1.1920929e-07f) {
-    for (int i = 0; i < 8; i++) coeffs[i] = 0;
-    coeffs[3] = 1;
-    return;
-  }
-  float sum = 0;
-  double y0 = -(x + 3) * M_PI * 0.25, s0 = sin(y0), c0 = cos(y0);
-  for (int i = 0; i < 8; i++) {
-    double y = -(x + 3 - i) * M_PI * 0.25;
-    coeffs[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y));
-    sum += coeffs[i];
-  }
-  sum = 1.f / sum;
-  for (int i = 0; i < 8; i++) coeffs[i] *= sum;
+// cv2's interpolation tables (cv_tables.hpp), built once on the host and uploaded once per device.  One allocation each:
+// IPA_CV_TABLE_ROWS 384 floats, IPA_CV_TABLE_U8_CUBIC 32 KB (remap_kernel keeps it in LDS), IPA_CV_TABLE_U8_LANCZOS4
+// 128 KB (remap_u8_lz_kernel keeps it in the LDS of a 1024-thread workgroup).
+static const std::vector<char>& cv_table_host(int which) {
+  static const std::vector<char> tabs[3] = {
+      [] { std::vector<char> t(cv_tables::kRowsFloats * 4); cv_tables::rows_table((float*)t.data()); return t; }(),
+      [] { std::vector<char> t(cv_tables::kTab2dDwords<4> * 4); cv_tables::fixed_tab2d<4>((int*)t.data()); return t; }(),
+      [] { std::vector<char> t(cv_tables::kTab2dDwords<8> * 4); cv_tables::fixed_tab2d<8>((int*)t.data()); return t; }()};
+  return tabs[which];
 }
 
-// OpenCV interpolateCubic (A = -0.75) in float32, the rows of cv2's bicubic table
-static void cubic_row_f32(float x, float* c) {
-#pragma clang fp contract(off)
-  const float A = -0.75f;
-  c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-  c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-  c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-  c[3] = 1.f - c[0] - c[1] - c[2];
-}
+static std::mutex g_cv_table_mu;
+static void* g_cv_table_dev[3][64] = {};
 
-static std::mutex g_lz_mu;
-static float* g_lanczos_dev[64] = {nullptr};
-
-int ipa_lanczos_table(ipa_ctx* ctx, const float** out) {
-  std::lock_guard<std::mutex> lk(g_lz_mu);
-  int dev = ctx->device;
-  IPA_REQUIRE(ctx, dev >= 0 && dev < 64, "device id out of range");
-  if (!g_lanczos_dev[dev]) {
-    // [0, 256): Lanczos4 rows; [256, 384): bicubic rows (the uint8 fixed-point path)
-    float tab[32 * 8 + 32 * 4];
-    for (int k = 0; k < 32; k++) lanczos4_row((float)k / 32.f, tab + k * 8);
-    for (int k = 0; k < 32; k++) cubic_row_f32((float)k * (1.f / 32), tab + 256 + k * 4);
-    float* d = nullptr;
-    IPA_HIP(ctx, hipSetDevice(dev));
-    IPA_HIP(ctx, hipMalloc((void**)&d, sizeof(tab)));
-    IPA_HIP(ctx, hipMemcpy(d, tab, sizeof(tab), hipMemcpyHostToDevice));
-    g_lanczos_dev[dev] = d;
-  }
-  *out = g_lanczos_dev[dev];
-  return IPA_OK;
-}
-
-// OpenCV's 8U bicubic weights as a table (imgwarp.cpp initInterTab2D, fixpt): per fraction pair
-// (fy, fx) the 4 x 4 shorts saturate_cast<short>(wy[k1] * wx[k2] * 2^15), their sum forced to 2^15
-// on one entry of the 2 x 2 block at (2, 2).  Device layout: row fy * 32 + fx = 8 dwords, per tap
-// row {w0 | w2 << 16, w1 | w3 << 16} - the operands of v_dot2_i32_i16 against the tap bytes
-// (b0, b2) and (b1, b3).  32 KB: remap_kernel keeps it in LDS.
-static int sat_short_f(float v) {
-  double r = nearbyint((double)v);  // cvRound: half to even
-  if (r < -32768.0) r = -32768.0;
-  if (r > 32767.0) r = 32767.0;
-  return (int)r;
-}
-
-static int* g_cubic2d_dev[64] = {};
-
-int ipa_u8_cubic_tab2d(ipa_ctx* ctx, const int** out) {
-#pragma clang fp contract(off)
-  std::lock_guard<std::mutex> lk(g_lz_mu);
+int ipa_cv_table_dev(ipa_ctx* ctx, int which, const void** out) {
+  std::lock_guard<std::mutex> lk(g_cv_table_mu);
   const int dev = ctx->device;
   IPA_REQUIRE(ctx, dev >= 0 && dev < 64, "device id out of range");
-  if (!g_cubic2d_dev[dev]) {
-    float t1[32][4];
-    for (int k = 0; k < 32; k++) cubic_row_f32((float)k * (1.f / 32), t1[k]);
-    static int packed[1024 * 8];
-    for (int fy = 0; fy < 32; fy++)
-      for (int fx = 0; fx < 32; fx++) {
-        int itab[16], isum = 0;
-        for (int k1 = 0; k1 < 4; k1++) {
-          const float vy = t1[fy][k1];
-          for (int k2 = 0; k2 < 4; k2++) {
-            const float v = vy * t1[fx][k2];
-            isum += itab[k1 * 4 + k2] = sat_short_f(v * 32768.f);
-          }
-        }
-        if (isum != 32768) {
-          const int diff = isum - 32768;
-          int Mk1 = 2, Mk2 = 2, mk1 = 2, mk2 = 2;
-          for (int k1 = 2; k1 < 4; k1++)
-            for (int k2 = 2; k2 < 4; k2++) {
-              if (itab[k1 * 4 + k2] < itab[mk1 * 4 + mk2]) { mk1 = k1; mk2 = k2; }
-              else if (itab[k1 * 4 + k2] > itab[Mk1 * 4 + Mk2]) { Mk1 = k1; Mk2 = k2; }
-            }
-          if (diff < 0) itab[Mk1 * 4 + Mk2] = (short)(itab[Mk1 * 4 + Mk2] - diff);
-          else itab[mk1 * 4 + mk2] = (short)(itab[mk1 * 4 + mk2] - diff);
-        }
-        int* row = packed + (fy * 32 + fx) * 8;
-        for (int r = 0; r < 4; r++) {
-          const int* w = itab + r * 4;
-          row[r * 2 + 0] = (w[0] & 0xffff) | (int)((unsigned)w[2] << 16);
-          row[r * 2 + 1] = (w[1] & 0xffff) | (int)((unsigned)w[3] << 16);
-        }
-      }
-    int* d = nullptr;
+  if (!g_cv_table_dev[which][dev]) {
+    const std::vector<char>& tab = cv_table_host(which);
+    void* d = nullptr;
     IPA_HIP(ctx, hipSetDevice(dev));
-    IPA_HIP(ctx, hipMalloc((void**)&d, sizeof(packed)));
-    IPA_HIP(ctx, hipMemcpy(d, packed, sizeof(packed), hipMemcpyHostToDevice));
-    g_cubic2d_dev[dev] = d;
+    IPA_HIP(ctx, hipMalloc(&d, tab.size()));
+    IPA_HIP(ctx, hipMemcpy(d, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    g_cv_table_dev[which][dev] = d;
   }
-  *out = g_cubic2d_dev[dev];
-  return IPA_OK;
-}
-
-// The same table for Lanczos4: per fraction pair 8 x 8 shorts = 32 dwords, per tap row
-// {w0 | w2 << 16, w1 | w3 << 16, w4 | w6 << 16, w5 | w7 << 16}.  128 KB: remap_u8_lz_kernel keeps
-// it in the LDS of a 1024-thread workgroup.
-static int* g_lz2d_dev[64] = {};
-
-int ipa_u8_lanczos_tab2d(ipa_ctx* ctx, const int** out) {
-#pragma clang fp contract(off)
-  std::lock_guard<std::mutex> lk(g_lz_mu);
-  const int dev = ctx->device;
-  IPA_REQUIRE(ctx, dev >= 0 && dev < 64, "device id out of range");
-  if (!g_lz2d_dev[dev]) {
-    float t1[32][8];
-    for (int k = 0; k < 32; k++) lanczos4_row((float)k * (1.f / 32), t1[k]);
-    static int packed[1024 * 32];
-    for (int fy = 0; fy < 32; fy++)
-      for (int fx = 0; fx < 32; fx++) {
-        int itab[64], isum = 0;
-        for (int k1 = 0; k1 < 8; k1++) {
-          const float vy = t1[fy][k1];
-          for (int k2 = 0; k2 < 8; k2++) {
-            const float v = vy * t1[fx][k2];
-            isum += itab[k1 * 8 + k2] = sat_short_f(v * 32768.f);
-          }
-        }
-        if (isum != 32768) {
-          const int diff = isum - 32768;
-          int Mk1 = 4, Mk2 = 4, mk1 = 4, mk2 = 4;
-          for (int k1 = 4; k1 < 6; k1++)
-            for (int k2 = 4; k2 < 6; k2++) {
-              if (itab[k1 * 8 + k2] < itab[mk1 * 8 + mk2]) { mk1 = k1; mk2 = k2; }
-              else if (itab[k1 * 8 + k2] > itab[Mk1 * 8 + Mk2]) { Mk1 = k1; Mk2 = k2; }
-            }
-          if (diff < 0) itab[Mk1 * 8 + Mk2] = (short)(itab[Mk1 * 8 + Mk2] - diff);
-          else itab[mk1 * 8 + mk2] = (short)(itab[mk1 * 8 + mk2] - diff);
-        }
-        int* row = packed + (fy * 32 + fx) * 32;
-        for (int r = 0; r < 8; r++)
-          for (int q = 0; q < 2; q++) {
-            const int* w = itab + r * 8 + 4 * q;
-            row[r * 4 + q * 2 + 0] = (w[0] & 0xffff) | (int)((unsigned)w[1] << 16);
-            row[r * 4 + q * 2 + 1] = (w[2] & 0xffff) | (int)((unsigned)w[3] << 16);
-          }
-      }
-    int* d = nullptr;
-    IPA_HIP(ctx, hipSetDevice(dev));
-    IPA_HIP(ctx, hipMalloc((void**)&d, sizeof(packed)));
-    IPA_HIP(ctx, hipMemcpy(d, packed, sizeof(packed), hipMemcpyHostToDevice));
-    g_lz2d_dev[dev] = d;
-  }
-  *out = g_lz2d_dev[dev];
+  *out = g_cv_table_dev[which][dev];
   return IPA_OK;
 }
 
@@ -216,42 +79,22 @@ int ipa_check_interp_border(ipa_ctx* ctx, int interp, int border) {
   return IPA_OK;
 }
 
-// host-pointer staging shared by the three remap flavours
+// the host-pointer remaps: argument checks, then source | result | map x | map y staged (the maps where given)
 struct Staged {
-  char* d_src; char* d_dst; float* d_mx; float* d_my;
-  size_t src_bytes, dst_bytes, map_bytes;
+  char* d[4];   // src, dst, mx, my
+  size_t dst_bytes;
 };
 
-static int stage_in(ipa_ctx* ctx, const void* src, int src_dt, int sh, int sw, int dst_dt, int dh,
-                    int dw, int n_frames, const float* mapx, const float* mapy, Staged* st) {
+static int remap_stage(ipa_ctx* ctx, const void* src, int src_dt, int sh, int sw, int dst_dt, int dh,
+                       int dw, int n_frames, const float* mapx, const float* mapy, Staged* st) {
   IPA_REQUIRE(ctx, src, "null source");
   IPA_REQUIRE(ctx, sh > 0 && sw > 0 && dh > 0 && dw > 0 && n_frames >= 1, "bad shape");
   size_t ss = ipa_dtype_size(src_dt), ds = ipa_dtype_size(dst_dt);
   IPA_REQUIRE(ctx, ss && ds, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  st->src_bytes = (size_t)sh * sw * ss * n_frames;
+  const size_t map_bytes = mapx ? (size_t)dh * dw * 4 : 0;
   st->dst_bytes = (size_t)dh * dw * ds * n_frames;
-  st->map_bytes = mapx ? (size_t)dh * dw * 4 : 0;
-  size_t total = up(st->src_bytes) + up(st->dst_bytes) + 2 * up(st->map_bytes);
-  int rc = ipa_ws_reserve(ctx, total);
-  if (rc) return rc;
-  char* b = (char*)ctx->ws;
-  st->d_src = b; b += up(st->src_bytes);
-  st->d_dst = b; b += up(st->dst_bytes);
-  st->d_mx = (float*)b; b += up(st->map_bytes);
-  st->d_my = (float*)b;
-  IPA_HIP(ctx, hipMemcpyAsync(st->d_src, src, st->src_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (mapx) {
-    IPA_HIP(ctx, hipMemcpyAsync(st->d_mx, mapx, st->map_bytes, hipMemcpyHostToDevice, ctx->stream));
-    IPA_HIP(ctx, hipMemcpyAsync(st->d_my, mapy, st->map_bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  return IPA_OK;
-}
-
-static int stage_out(ipa_ctx* ctx, void* dst, const Staged& st) {
-  IPA_HIP(ctx, hipMemcpyAsync(dst, st.d_dst, st.dst_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_in(ctx, {{src, (size_t)sh * sw * ss * n_frames}, {nullptr, st->dst_bytes}, {mapx, map_bytes},
+                            {mapy, map_bytes}}, st->d);
 }
 
 // the float32 maps of a lens model, kept in the context until another model or size is asked for
@@ -267,19 +110,10 @@ int ipa_lens_map_cached(ipa_ctx* ctx, const double* K, const double* dist5, cons
   const bool hit = ctx->lens_key_n == 25 && memcmp(ctx->lens_key, key, sizeof(key)) == 0;
   if (!hit) {
     ctx->lens_key_n = 0;
-    if (ctx->lens_map_bytes < 2 * mb) {
-      IPA_HIP(ctx, hipSetDevice(ctx->device));
-      IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier calls may still read the old maps
-      if (ctx->lens_map) {
-        IPA_HIP(ctx, hipFree(ctx->lens_map));
-        ctx->lens_map = nullptr;
-        ctx->lens_map_bytes = 0;
-      }
-      IPA_HIP(ctx, hipMalloc(&ctx->lens_map, 2 * mb));
-      ctx->lens_map_bytes = 2 * mb;
-    }
-    int rc = ipa_build_undistort_map_dev(ctx, K, dist5, newK, h, w, (float*)ctx->lens_map,
-                                         (float*)((char*)ctx->lens_map + mb), w);
+    int rc = ipa_grow_reserve(ctx, &ctx->lens_map, &ctx->lens_map_bytes, 2 * mb, 2 * mb);   // earlier calls may still read the old maps
+    if (rc) return rc;
+    rc = ipa_build_undistort_map_dev(ctx, K, dist5, newK, h, w, (float*)ctx->lens_map,
+                                     (float*)((char*)ctx->lens_map + mb), w);
     if (rc) return rc;
     memcpy(ctx->lens_key, key, sizeof(key));
     ctx->lens_key_n = 25;
@@ -313,17 +147,13 @@ int ipa_build_undistort_map(ipa_ctx* ctx, const double* K, const double* dist5,
                             const double* newK, int h, int w, float* mapx, float* mapy) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mapx && mapy && h > 0 && w > 0, "bad map arguments");
-  size_t mb = ((size_t)h * w * 4 + 255) & ~(size_t)255;
-  int rc = ipa_ws_reserve(ctx, 2 * mb);
+  const size_t mb = (size_t)h * w * 4;
+  char* d[2];
+  int rc = ipa_stage_in(ctx, {{nullptr, mb}, {nullptr, mb}}, d);
   if (rc) return rc;
-  float* dx = (float*)ctx->ws;
-  float* dy = (float*)((char*)ctx->ws + mb);
-  rc = ipa_build_undistort_map_dev(ctx, K, dist5, newK, h, w, dx, dy, w);
+  rc = ipa_build_undistort_map_dev(ctx, K, dist5, newK, h, w, (float*)d[0], (float*)d[1], w);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(mapx, dx, (size_t)h * w * 4, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(mapy, dy, (size_t)h * w * 4, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{mapx, d[0], mb}, {mapy, d[1], mb}});
 }
 
 // Round 6 (knob strip_remap): bilinear remaps of uint16 frames INTO float32 - camera frames as
@@ -347,22 +177,6 @@ static bool strip_remap_takes(const ipa_ctx* ctx, const void* d_src, const void*
   if (sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || src_pitch < sw || dst_pitch < dw || src_pitch >= (1l << 23)) return false;
   if (((size_t)(sh - 1) * src_pitch + sw) * ipa_dtype_size(src_dtype) >= (1ull << 31) || n_frames < 1 || n_frames > 65535) return false;
   return true;
-}
-// how far the source row moves along one output row (px per px), at 9 points of the picture
-static double warp_row_drift(const double* m, int dh, int dw) {
-  double drift = 0;
-  for (int py = 0; py < 3; py++)
-    for (int px = 0; px < 3; px++) {
-      const double u = (dw - 2) * 0.5 * px, v = (dh - 2) * 0.5 * py;
-      double y[2];
-      for (int i = 0; i < 2; i++) {
-        const double W = m[6] * (u + i) + m[7] * v + m[8];
-        y[i] = (m[3] * (u + i) + m[4] * v + m[5]) * (W != 0.0 ? 1.0 / W : 0.0);
-      }
-      if (!(fabs(y[1] - y[0]) < 1e6)) return 1e6;
-      drift = fabs(y[1] - y[0]) > drift ? fabs(y[1] - y[0]) : drift;
-    }
-  return drift;
 }
 static const double kOneTap = 1.0;
 
@@ -438,7 +252,7 @@ int ipa_warp_perspective_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
   IPA_REQUIRE(ctx, M, "null matrix");
   if (strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp,
                         2, false) &&
-      warp_row_drift(M, dh, dw) < 0.2) {   // (see ipa_remap_dev; pictures that turn stay with the gather kernels)
+      homography_row_drift(M, dh, dw) < 0.2) {   // (see ipa_remap_dev; pictures that turn stay with the gather kernels)
     ctx->strip_remaps++;
     return ipa_warp_perspective_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, &kOneTap, 1, &kOneTap, 1,
                                               d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
@@ -465,19 +279,26 @@ int ipa_warp_grid_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, in
   return ipa_remap_launch_grid(ctx, a, cell_rects, cell_M, n_cells);
 }
 
+int ipa_cv_table(int which, void* out, size_t cap) {
+  if (which < IPA_CV_TABLE_ROWS || which > IPA_CV_TABLE_U8_LANCZOS4) return -1;
+  const std::vector<char>& tab = cv_table_host(which);
+  if (out && cap >= tab.size()) memcpy(out, tab.data(), tab.size());
+  return (int)tab.size();
+}
+
 int ipa_remap(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const float* mapx,
               const float* mapy, void* dst, int dst_dtype, int dh, int dw, int n_frames,
               int interp, int border_mode, double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, mapx && mapy && dst, "null pointer");
   Staged st;
-  int rc = stage_in(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, mapx, mapy, &st);
+  int rc = remap_stage(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, mapx, mapy, &st);
   if (rc) return rc;
-  rc = ipa_remap_dev(ctx, st.d_src, src_dtype, sh, sw, sw, st.d_mx, st.d_my, dw, st.d_dst,
+  rc = ipa_remap_dev(ctx, st.d[0], src_dtype, sh, sw, sw, (const float*)st.d[2], (const float*)st.d[3], dw, st.d[1],
                      dst_dtype, dh, dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp,
                      border_mode, border_value);
   if (rc) return rc;
-  return stage_out(ctx, dst, st);
+  return ipa_stage_out(ctx, {{dst, st.d[1], st.dst_bytes}});
 }
 
 int ipa_undistort(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const double* K,
@@ -486,13 +307,13 @@ int ipa_undistort(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, 
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, dst, "null pointer");
   Staged st;
-  int rc = stage_in(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
+  int rc = remap_stage(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
   if (rc) return rc;
-  rc = ipa_undistort_dev(ctx, st.d_src, src_dtype, sh, sw, sw, K, dist5, newK, st.d_dst, dst_dtype,
+  rc = ipa_undistort_dev(ctx, st.d[0], src_dtype, sh, sw, sw, K, dist5, newK, st.d[1], dst_dtype,
                          dh, dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp, border_mode,
                          border_value);
   if (rc) return rc;
-  return stage_out(ctx, dst, st);
+  return ipa_stage_out(ctx, {{dst, st.d[1], st.dst_bytes}});
 }
 
 int ipa_warp_perspective(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw,
@@ -501,13 +322,13 @@ int ipa_warp_perspective(ipa_ctx* ctx, const void* src, int src_dtype, int sh, i
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, dst, "null pointer");
   Staged st;
-  int rc = stage_in(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
+  int rc = remap_stage(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
   if (rc) return rc;
-  rc = ipa_warp_perspective_dev(ctx, st.d_src, src_dtype, sh, sw, sw, M, st.d_dst, dst_dtype, dh,
+  rc = ipa_warp_perspective_dev(ctx, st.d[0], src_dtype, sh, sw, sw, M, st.d[1], dst_dtype, dh,
                                 dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp,
                                 border_mode, border_value);
   if (rc) return rc;
-  return stage_out(ctx, dst, st);
+  return ipa_stage_out(ctx, {{dst, st.d[1], st.dst_bytes}});
 }
 
 int ipa_warp_grid(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, const int* cell_rects,
@@ -516,13 +337,13 @@ int ipa_warp_grid(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, 
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, dst, "null pointer");
   Staged st;
-  int rc = stage_in(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
+  int rc = remap_stage(ctx, src, src_dtype, sh, sw, dst_dtype, dh, dw, n_frames, nullptr, nullptr, &st);
   if (rc) return rc;
-  rc = ipa_warp_grid_dev(ctx, st.d_src, src_dtype, sh, sw, sw, cell_rects, cell_M, n_cells, st.d_dst,
+  rc = ipa_warp_grid_dev(ctx, st.d[0], src_dtype, sh, sw, sw, cell_rects, cell_M, n_cells, st.d[1],
                          dst_dtype, dh, dw, dw, n_frames, (long)sh * sw, (long)dh * dw, interp,
                          border_mode, border_value);
   if (rc) return rc;
-  return stage_out(ctx, dst, st);
+  return ipa_stage_out(ctx, {{dst, st.d[1], st.dst_bytes}});
 }
 
 }  // extern "C"

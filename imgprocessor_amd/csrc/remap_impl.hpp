@@ -308,9 +308,7 @@ build_map_kernel(UndistortCoord c, int h, int w, float* mapx, float* mapy, long 
 using namespace ipa;
 
 int ipa_check_interp_border(ipa_ctx* ctx, int interp, int border);  // remap.hip
-int ipa_lanczos_table(ipa_ctx* ctx, const float** out);               // remap.hip
-int ipa_u8_cubic_tab2d(ipa_ctx* ctx, const int** out);                // remap.hip
-int ipa_u8_lanczos_tab2d(ipa_ctx* ctx, const int** out);              // remap.hip
+int ipa_cv_table_dev(ipa_ctx* ctx, int which, const void** out);      // remap.hip: the device copy of ipa_cv_table(which)
 
 struct RemapCall {
   const void* src; int src_dt; int sh, sw; long spitch;
@@ -432,14 +430,6 @@ static void launch_rest(ipa_ctx* ctx, const RemapParams& p, const Coord& c, int 
                          ctx->stream, p, c);
       break;
   }
-}
-
-static inline bool aligned_rows(const void* base, long pitch_elems, long frame_elems, int n_frames,
-                         size_t elem, size_t vec_bytes) {
-  if (((uintptr_t)base) % vec_bytes) return false;
-  if ((pitch_elems * (long)elem) % (long)vec_bytes) return false;
-  if (n_frames > 1 && (frame_elems * (long)elem) % (long)vec_bytes) return false;
-  return true;
 }
 
 // plan + ring kernel for the clean strips of a batch; sets p.skip for remap_kernel.
@@ -746,7 +736,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
   p.tab2d = nullptr;
   const bool u8_cubic_tab = base == IPA_INTER_CUBIC_CV && a.src_dt == IPA_U8 && a.dst_dt == IPA_U8;
   if (u8_cubic_tab) {
-    rc = ipa_u8_cubic_tab2d(ctx, &p.tab2d);
+    rc = ipa_cv_table_dev(ctx, IPA_CV_TABLE_U8_CUBIC, (const void**)&p.tab2d);
     if (rc) return rc;
   }
   // a piecewise source (GridCoord) takes only the plain gather launch: the ring kernel, the
@@ -756,7 +746,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
   const bool u8_lz_tab = !kPiece && base == IPA_INTER_LANCZOS4 && a.src_dt == IPA_U8 &&
                          a.dst_dt == IPA_U8 && ctx->tune.u8_lz_lds;
   if (u8_lz_tab) {
-    rc = ipa_u8_lanczos_tab2d(ctx, &p.tab2d);
+    rc = ipa_cv_table_dev(ctx, IPA_CV_TABLE_U8_LANCZOS4, (const void**)&p.tab2d);
     if (rc) return rc;
   }
   // uint16 -> uint16 in a cv2 mode (1/32-px coordinates: linear_cv_q5, cubic_cv_q5, lanczos4):
@@ -766,7 +756,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
                       (base == IPA_INTER_LANCZOS4 ||
                        (p.q5 && (base == IPA_INTER_LINEAR || base == IPA_INTER_CUBIC_CV)));
   if (base == IPA_INTER_LANCZOS4 || (u16_cv && base == IPA_INTER_CUBIC_CV)) {
-    rc = ipa_lanczos_table(ctx, &p.lanczos);
+    rc = ipa_cv_table_dev(ctx, IPA_CV_TABLE_ROWS, (const void**)&p.lanczos);
     if (rc) return rc;
   }
   p.cval = a.cval;

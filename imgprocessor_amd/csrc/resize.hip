@@ -17,11 +17,11 @@
 //   * INTER_AREA, integer scale: the block summed in groups of four, times (float)(1 / area);
 //     otherwise computeResizeAreaTab's decimation tables (float32 weights), row sums first.
 //     INTER_AREA upscaling (a bilinear variant in OpenCV) is not built.
-#include <cfloat>
 #include <cmath>
 #include <vector>
 
 #include "common.hpp"
+#include "cv_tables.hpp"
 #include "interp_paths.hpp"
 #include "launch.hpp"
 
@@ -240,35 +240,6 @@ fast_filter_stat_kernel(const T* __restrict__ arr, long pitch, int gx, int gy, i
 }
 
 // ------------------------------------------------------------- host: coefficient tables --
-static void cubic_coeffs(float x, float* c) {
-  const float A = -0.75f;
-  c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-  c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-  c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-  c[3] = 1.f - c[0] - c[1] - c[2];
-}
-
-// OpenCV's interpolateLanczos4: float coefficients from double sines, normalised in float
-static void lanczos4_coeffs(float x, float* c) {
-  static const double s45 = 0.70710678118654752440084436210485;
-  static const double cs[][2] = {{1, 0},  {-s45, -s45}, {0, 1},  {s45, -s45},
-                                 {-1, 0}, {s45, s45},   {0, -1}, {-s45, s45}};
-  if (x < FLT_EPSILON) {
-    for (int i = 0; i < 8; i++) c[i] = 0;
-    c[3] = 1;
-    return;
-  }
-  float sum = 0;
-  const double y0 = -(x + 3) * M_PI * 0.25, s0 = sin(y0), c0 = cos(y0);
-  for (int i = 0; i < 8; i++) {
-    const double y = -(x + 3 - i) * M_PI * 0.25;
-    c[i] = (float)((cs[i][0] * s0 + cs[i][1] * c0) / (y * y));
-    sum += c[i];
-  }
-  sum = 1.f / sum;
-  for (int i = 0; i < 8; i++) c[i] *= sum;
-}
-
 static void axis_tables(int ssize, int dsize, double scale, int interp, int ks, bool clamp_x,
                         std::vector<int>& ofs, std::vector<float>& coef, int* pmax) {
   ofs.resize(dsize);
@@ -287,8 +258,8 @@ static void axis_tables(int ssize, int dsize, double scale, int interp, int ks, 
     }
     ofs[d] = s;
     float* c = coef.data() + (size_t)d * ks;
-    if (interp == IPA_RESIZE_CUBIC) cubic_coeffs(f, c);
-    else if (interp == IPA_RESIZE_LANCZOS4) lanczos4_coeffs(f, c);
+    if (interp == IPA_RESIZE_CUBIC) cv_tables::cubic_row(f, c);
+    else if (interp == IPA_RESIZE_LANCZOS4) cv_tables::lanczos4_row(f, c);
     else { c[0] = 1.f - f; c[1] = f; }
   }
   if (pmax) *pmax = xmax;
@@ -439,18 +410,13 @@ int ipa_resize(ipa_ctx* ctx, const void* src, int dtype, int sh, int sw, void* d
   IPA_REQUIRE(ctx, src && dst && sh > 0 && sw > 0 && dh > 0 && dw > 0, "bad arguments");
   const size_t es = ipa_dtype_size(dtype);
   IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t sb = (size_t)sh * sw * es, db = (size_t)dh * dw * es;
-  int rc = ipa_ws_reserve(ctx, up(sb) + up(db));
+  char* d[2];   // source, result
+  int rc = ipa_stage_in(ctx, {{src, sb}, {nullptr, db}}, d);
   if (rc) return rc;
-  char* ds = (char*)ctx->ws;
-  char* dd = ds + up(sb);
-  IPA_HIP(ctx, hipMemcpyAsync(ds, src, sb, hipMemcpyHostToDevice, ctx->stream));
-  rc = ipa_resize_dev(ctx, ds, dtype, sh, sw, sw, dd, dh, dw, dw, interp);
+  rc = ipa_resize_dev(ctx, d[0], dtype, sh, sw, sw, d[1], dh, dw, dw, interp);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(dst, dd, db, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{dst, d[1], db}});
 }
 
 int ipa_fast_filter_stat_dev(ipa_ctx* ctx, const void* d_arr, int dtype, int h, int w, long pitch,
@@ -480,19 +446,14 @@ int ipa_fast_filter_stat(ipa_ctx* ctx, const void* arr, int dtype, int h, int w,
   IPA_REQUIRE(ctx, arr && out && h > 0 && w > 0 && every >= 1, "bad arguments");
   const size_t es = ipa_dtype_size(dtype);
   IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t sb = (size_t)h * w * es;
   const size_t ob = (size_t)((h + every - 1) / every) * ((w + every - 1) / every) * 8;
-  int rc = ipa_ws_reserve(ctx, up(sb) + up(ob));
+  char* d[2];   // array, statistics
+  int rc = ipa_stage_in(ctx, {{arr, sb}, {nullptr, ob}}, d);
   if (rc) return rc;
-  char* ds = (char*)ctx->ws;
-  double* dd = (double*)(ds + up(sb));
-  IPA_HIP(ctx, hipMemcpyAsync(ds, arr, sb, hipMemcpyHostToDevice, ctx->stream));
-  rc = ipa_fast_filter_stat_dev(ctx, ds, dtype, h, w, w, ksize, every, fn, dd);
+  rc = ipa_fast_filter_stat_dev(ctx, d[0], dtype, h, w, w, ksize, every, fn, (double*)d[1]);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(out, dd, ob, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{out, d[1], ob}});
 }
 
 }  // extern "C"

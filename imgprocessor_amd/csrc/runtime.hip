@@ -348,57 +348,51 @@ int ipa_event_elapsed_ms(ipa_ctx* c, ipa_event* a, ipa_event* b, float* ms) {
 
 }  // extern "C"
 
-int ipa_ws_reserve(ipa_ctx* c, size_t bytes) {
-  if (c->ws_bytes >= bytes) return IPA_OK;
+int ipa_grow_reserve(ipa_ctx* c, void** buf, size_t* have, size_t bytes, size_t want) {
+  if (*have >= bytes) return IPA_OK;
   IPA_HIP(c, hipSetDevice(c->device));
-  IPA_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->ws) {
-    IPA_HIP(c, hipFree(c->ws));
-    c->ws = nullptr;
-    c->ws_bytes = 0;
+  IPA_HIP(c, hipStreamSynchronize(c->stream));  // earlier calls may still use the old buffer
+  if (*buf) {
+    IPA_HIP(c, hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
   }
-  size_t want = bytes + (bytes >> 2) + (1u << 20);
-  IPA_HIP(c, hipMalloc(&c->ws, want));
-  c->ws_bytes = want;
+  IPA_HIP(c, hipMalloc(buf, want));
+  *have = want;
   return IPA_OK;
 }
 
-int ipa_fill_stage(ipa_ctx* ctx, const void* grid, int dtype, const uint8_t* mask, int h, int w,
-                   char** d_grid, uint8_t** d_mask, size_t* gb) {
-  IPA_REQUIRE(ctx, grid && h > 0 && w > 0, "bad arguments");
-  const size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  *gb = (size_t)h * w * es;
-  int rc = ipa_ws_reserve(ctx, up(*gb) + up((size_t)h * w));
-  if (rc) return rc;
-  IPA_HIP(ctx, hipSetDevice(ctx->device));  // the reservation selects it only when it grows
-  *d_grid = (char*)ctx->ws;
-  *d_mask = (uint8_t*)(*d_grid + up(*gb));
-  IPA_HIP(ctx, hipMemcpyAsync(*d_grid, grid, *gb, hipMemcpyHostToDevice, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(*d_mask, mask, (size_t)h * w, hipMemcpyHostToDevice, ctx->stream));
-  return IPA_OK;
-}
-
-int ipa_fill_back(ipa_ctx* ctx, void* grid, const char* d_grid, size_t gb) {
-  IPA_HIP(ctx, hipMemcpyAsync(grid, d_grid, gb, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+int ipa_ws_reserve(ipa_ctx* c, size_t bytes) {
+  return ipa_grow_reserve(c, &c->ws, &c->ws_bytes, bytes, bytes + (bytes >> 2) + (1u << 20));
 }
 
 int ipa_plan_reserve(ipa_ctx* c, size_t bytes) {
   c->plan_key_n = 0;  // the caller overwrites the buffer
-  if (c->plan_bytes >= bytes) return IPA_OK;
-  IPA_HIP(c, hipSetDevice(c->device));
-  IPA_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->plan) {
-    IPA_HIP(c, hipFree(c->plan));
-    c->plan = nullptr;
-    c->plan_bytes = 0;
+  return ipa_grow_reserve(c, &c->plan, &c->plan_bytes, bytes, bytes + (bytes >> 1) + (1u << 16));
+}
+
+static size_t stage_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int ipa_stage_in(ipa_ctx* ctx, std::initializer_list<ipa_stage_slot> slots, char** d) {
+  size_t total = 0;
+  for (const ipa_stage_slot& s : slots) total += stage_up(s.bytes);
+  int rc = ipa_ws_reserve(ctx, total);
+  if (rc) return rc;
+  IPA_HIP(ctx, hipSetDevice(ctx->device));  // the reservation selects it only when it grows
+  char* b = (char*)ctx->ws;
+  for (const ipa_stage_slot& s : slots) {
+    *d = s.bytes ? b : nullptr;
+    if (s.host && s.bytes) IPA_HIP(ctx, hipMemcpyAsync(b, s.host, s.bytes, hipMemcpyHostToDevice, ctx->stream));
+    b += stage_up(s.bytes);
+    d++;
   }
-  size_t want = bytes + (bytes >> 1) + (1u << 16);
-  IPA_HIP(c, hipMalloc(&c->plan, want));
-  c->plan_bytes = want;
+  return IPA_OK;
+}
+
+int ipa_stage_out(ipa_ctx* ctx, std::initializer_list<ipa_stage_back> backs) {
+  for (const ipa_stage_back& k : backs)
+    IPA_HIP(ctx, hipMemcpyAsync(k.host, k.dev, k.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return IPA_OK;
 }
 

@@ -968,7 +968,7 @@ __device__ __forceinline__ uint8_t sample_u8_lanczos_lds(const SrcView& s, const
 //                         exists (rows, columns through the border mode)  sum += (S - cv) * w;
 //   * saturate_cast<ushort>(sum) = round half to even, clamp to [0, 65535].
 // `tab`: the float32 1-D tables ([0, 256) Lanczos4 rows, [256, 384) bicubic rows) of
-// ipa_lanczos_table.  Unpinned against cv2 like the other cv2 modes: the
+// IPA_CV_TABLE_ROWS.  Unpinned against cv2 like the other cv2 modes: the
 // expression order is restated from memory of the OpenCV 4.x source.
 template <int INTERP, typename C>
 __device__ __forceinline__ uint16_t sample_u16_cv(const SrcView& s, const float* tab, C sx, C sy,

@@ -158,6 +158,21 @@ int ipa_remap(ipa_ctx* ctx, const void* src, int src_dtype, int sh, int sw, cons
               const float* mapy, void* dst, int dst_dtype, int dh, int dw, int n_frames,
               int interp, int border_mode, double border_value);
 
+/* The tables of OpenCV's remap at 1/32 px that the cv2 modes read, exactly the bytes the library uploads
+ * (csrc/cv_tables.hpp).  Host only: needs neither a context nor a device.  Returns the table's size in bytes, -1 for an
+ * unknown `which`; the table is written to `out` when that is given and `cap` >= the size, nothing otherwise. */
+typedef enum {
+  IPA_CV_TABLE_ROWS = 0,        /* 384 float32: 32 x 8 Lanczos4 rows (interpolateLanczos4 at k / 32), then 32 x 4
+                                   bicubic rows (interpolateCubic, A = -0.75) */
+  IPA_CV_TABLE_U8_CUBIC = 1,    /* uint8 bicubic, 1024 x 8 int32: entry fy * 32 + fx holds the 4 x 4 int16 weights
+                                   cvRound(wy[r] * wx[c] * 2^15) whose sum is forced to 2^15 (initInterTab2D, fixed
+                                   point); tap row r = dwords 2 r, 2 r + 1 = {w0 | w2 << 16, w1 | w3 << 16}
+                                   (low half | high half) */
+  IPA_CV_TABLE_U8_LANCZOS4 = 2  /* uint8 Lanczos4, 1024 x 32 int32: the 8 x 8 weights likewise; tap row r = dwords
+                                   4 r .. 4 r + 3 = {w0 | w1 << 16, w2 | w3 << 16, w4 | w5 << 16, w6 | w7 << 16} */
+} ipa_cv_table_id;
+int ipa_cv_table(int which, void* out, size_t cap);
+
 /* LensDistortion.correct without materialised maps: the distortion model of
  * initUndistortRectifyMap is evaluated per pixel in double, rounded to the
  * float32 a CV_32FC1 map would hold, then sampled exactly like ipa_remap.
