@@ -34,6 +34,10 @@ CONV_CONV2D, CONV_SEPCONV2D, CONV_SEPCONV2D_LDS = range(3)
 (INTERP_K_CROSS_SEG, INTERP_K_CROSS_BALLOT_STEPS, INTERP_K_CROSS_SEARCH_PASS,
  INTERP_K_FASTDIV_SHIFT, INTERP_K_PS_WAVES, INTERP_K_PS_MAX_ROWS, INTERP_K_STAT_MAX) = range(7)
 
+# ipa_resize_interp of ipa_resize (cv2's INTER_* numbers); the `fn` of ipa_fast_filter_stat
+RESIZE_LINEAR, RESIZE_CUBIC, RESIZE_AREA, RESIZE_LANCZOS4 = 1, 2, 3, 4
+STAT_MEDIAN, STAT_NANMEDIAN, STAT_MEAN, STAT_NANMEAN = range(4)
+
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t

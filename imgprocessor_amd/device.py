@@ -91,9 +91,8 @@ class Context(object):
         return old
 
     def get_tuning(self, name):
-        import ctypes
-        v = ctypes.c_int(0)
-        self._check(self._lib.ipa_ctx_get_tuning(self.handle, name.encode(), ctypes.byref(v)),
+        v = C.c_int(0)
+        self._check(self._lib.ipa_ctx_get_tuning(self.handle, name.encode(), C.byref(v)),
                     'get_tuning')
         return v.value
 
@@ -176,13 +175,8 @@ class Context(object):
         w = 3840
         rows = (nbytes // 2) // (4 * w)
 
-        def view(off):
-            v = DeviceArray.__new__(DeviceArray)
-            v.ctx, v.shape, v.dtype, v.nbytes = self, (rows, w), np.dtype(np.float32), rows * w * 4
-            v.ptr = C.c_void_p(ptr.value + off)
-            v._owner = False
-            return v
-        lo, hi = view(0), view(rows * w * 4)
+        lo, hi = (DeviceArray._wrap(self, C.c_void_p(ptr.value + off), (rows, w), np.float32, False)
+                  for off in (0, rows * w * 4))
         k3 = np.full((3, 3), 1.0 / 9)
         for _ in range(2):
             ops.conv2d(lo, k3, out=hi)
@@ -328,13 +322,19 @@ class DeviceArray(object):
     def counts(cls, ctx, shape):
         """int32 per-pixel counts: the state of ops.ste_update.  No kernel takes int32 images, so
         the constructor refuses that dtype; this is the one way to allocate it."""
+        return cls._wrap(ctx, ctx._alloc(int(np.prod(shape, dtype=np.int64)) * 4), shape, np.int32, True)
+
+    @classmethod
+    def _wrap(cls, ctx, ptr, shape, dtype, owner, base=None):
+        """an array over device memory that exists already (nothing is allocated, any dtype):
+        `owner` - free() gives the block back to the context; `base` - the array a view was cut
+        from, kept alive with it"""
         a = cls.__new__(cls)
-        a.ctx = ctx
-        a.shape = tuple(int(s) for s in shape)
-        a.dtype = np.dtype(np.int32)
-        a.nbytes = int(np.prod(a.shape, dtype=np.int64)) * 4
-        a.ptr = ctx._alloc(a.nbytes)
-        a._owner = True
+        a.ctx, a.ptr, a._owner = ctx, ptr, owner
+        a.shape, a.dtype = tuple(int(s) for s in shape), np.dtype(dtype)
+        a.nbytes = int(np.prod(a.shape, dtype=np.int64)) * a.dtype.itemsize
+        if base is not None:
+            a._base = base
         return a
 
     @property
@@ -375,13 +375,9 @@ class DeviceArray(object):
         """view of frame i of a (n, h, w) batch (no copy, not owning)"""
         if self.ndim != 3:
             raise ValueError('frame() needs a (n,h,w) batch')
-        v = DeviceArray.__new__(DeviceArray)
-        v.ctx, v.shape, v.dtype = self.ctx, self.shape[1:], self.dtype
-        v.nbytes = self.nbytes // self.shape[0]
-        v.ptr = C.c_void_p(self.ptr.value + i * v.nbytes)
-        v._owner = False
-        v._base = self
-        return v
+        off = i * (self.nbytes // self.shape[0])
+        return DeviceArray._wrap(self.ctx, C.c_void_p(self.ptr.value + off), self.shape[1:], self.dtype,
+                                 False, base=self)
 
     def free(self):
         if getattr(self, '_owner', False) and self.ptr is not None and self.ctx.handle is not None:

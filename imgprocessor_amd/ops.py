@@ -72,6 +72,20 @@ def _p(a):
     return a.ptr if _is_dev(a) else a.ctypes.data_as(C.c_void_p)
 
 
+def _dptr(a):
+    """const double* to a C-contiguous float64 ndarray (the pointer keeps the array alive)"""
+    return a.ctypes.data_as(L._dp)
+
+
+def _mat3(M):
+    return L.dbl(np.ravel(np.asarray(M, dtype=np.float64)), 9)
+
+
+def _lens(K, dist5, newK):
+    """K, dist5 = [k1, k2, p1, p2, k3], newK as the exports take them"""
+    return L.dbl(np.ravel(K), 9), L.dbl(np.ravel(dist5)[:5], 5), L.dbl(np.ravel(newK), 9)
+
+
 def _out_dtype(src_dtype, out_dtype):
     return np.dtype(src_dtype if out_dtype is None else out_dtype)
 
@@ -116,7 +130,7 @@ def build_undistort_map(K, dist5, newK, h, w, ctx=None, device=False):
     """cv2.initUndistortRectifyMap(K, d, None, newK, (w,h), CV_32FC1)"""
     ctx = ctx or default_context()
     lib = ctx._lib
-    K, d, nK = L.dbl(np.ravel(K), 9), L.dbl(np.ravel(dist5)[:5], 5), L.dbl(np.ravel(newK), 9)
+    K, d, nK = _lens(K, dist5, newK)
     if device:
         mx, my = DeviceArray(ctx, (h, w), np.float32), DeviceArray(ctx, (h, w), np.float32)
         ctx._check(lib.ipa_build_undistort_map_dev(ctx.handle, K, d, nK, h, w, mx.ptr, my.ptr, w),
@@ -141,16 +155,76 @@ def _check_dev_maps(mapx, mapy):
 
 
 # ----------------------------------------------------------------- remap --
+def _fused_dtype(src_dtype, separable):
+    """what the remap -> filter chains write: float64 for float64 frames under a dense kernel,
+    float32 for everything else and for every separable chain"""
+    return np.dtype(np.float64 if not separable and src_dtype == np.float64 else np.float32)
+
+
+def _dense_filt(kernel, conv_mode):
+    k = np.ascontiguousarray(kernel, dtype=np.float64)
+    return (_dptr(k), k.shape[0], k.shape[1]), conv_mode, False
+
+
+def _sep_filt(ky, kx, conv_mode):
+    ky = np.ascontiguousarray(ky, dtype=np.float64).ravel()
+    kx = np.ascontiguousarray(kx, dtype=np.float64).ravel()
+    return (_dptr(ky), ky.size, _dptr(kx), kx.size), conv_mode, True
+
+
+def _geometry(name, src, coords, out_hw, interpolation, border_mode, border_value, out_dtype, out,
+              ctx, filt=None):
+    """The call that remap, undistort, warp_perspective, warp_grid and their chains share:
+    ipa_<name>_dev for a DeviceArray source, the host-pointer ipa_<name> for anything else.
+    Either takes the source (pointer, dtype, h, w[, pitch]), then `coords` - the export's own
+    middle (maps, lens model, matrix, cells) in the form that goes with the source - then
+    `filt` for a chain (_dense_filt / _sep_filt), then the result (pointer, dtype, h, w[, pitch])
+    with the frame count[, frame strides], the sampling and the filter's border pair.  Arrays
+    are dense: pitches are the widths, frame strides h * w.  out_hw None: the source's shape."""
+    interp, border = interp_id(interpolation), border_id(border_mode)
+    dev = _is_dev(src)
+    ctx = _ctx_of(src, ctx=ctx)
+    if not dev:
+        src = _host(src)
+    n, sh, sw = as_frames(src)
+    dh, dw = out_hw or (sh, sw)
+    if filt is None:
+        taps, conv, odt = (), (), _out_dtype(src.dtype, out_dtype)
+    else:
+        taps, conv_mode, separable = filt
+        conv, odt = (border_id(conv_mode),) * 2, _fused_dtype(src.dtype, separable)
+    oshape = (dh, dw) if len(src.shape) == 2 else (n, dh, dw)
+    sampling = (interp, border, float(border_value)) + conv
+    if dev:
+        dst = _dev_out(ctx, out, oshape, odt)
+        status = getattr(ctx._lib, 'ipa_%s_dev' % name)(
+            ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw, *coords, *taps,
+            dst.ptr, dtype_id(odt), dh, dw, dw, n, sh * sw, dh * dw, *sampling)
+    else:
+        dst = np.empty(oshape, odt)
+        status = getattr(ctx._lib, 'ipa_%s' % name)(
+            ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, *coords,
+            _p(dst), dtype_id(odt), dh, dw, n, *sampling)
+    ctx._check(status, name)
+    return dst
+
+
+def _dev_only(name, ctx, *arrs):
+    """the chains take DeviceArrays only -> their context"""
+    ctx = _ctx_of(*arrs, ctx=ctx)
+    if not all(_is_dev(a) for a in arrs):
+        raise TypeError('%s works on DeviceArrays (use Context.to_device)' % name)
+    return ctx
+
+
 def remap(src, mapx, mapy, interpolation='linear', border_mode='constant', border_value=0.0,
           out_dtype=None, out=None, ctx=None, map_roi=None):
     """cv2.remap(src, mapx, mapy, ...).  map_roi=(x, y, w, h) (device maps only)
     evaluates just that window of the maps — the keepSize=False crop of
     LensDistortion.correct without computing the discarded border."""
-    interp, border = interp_id(interpolation), border_id(border_mode)
     if _is_dev(src):
         ctx = _ctx_of(src, mapx, mapy, ctx=ctx)
         _check_dev_maps(mapx, mapy)
-        n, sh, sw = as_frames(src)
         mh, mw = mapx.shape
         dh, dw, moff = mh, mw, 0
         if map_roi is not None:
@@ -158,87 +232,34 @@ def remap(src, mapx, mapy, interpolation='linear', border_mode='constant', borde
             if not (0 <= rx and 0 <= ry and rw > 0 and rh > 0 and rx + rw <= mw and ry + rh <= mh):
                 raise ValueError('map_roi %s outside the %dx%d maps' % (map_roi, mh, mw))
             dh, dw, moff = rh, rw, (ry * mw + rx) * 4
-        odt = _out_dtype(src.dtype, out_dtype)
-        oshape = (dh, dw) if src.ndim == 2 else (n, dh, dw)
-        dst = _dev_out(ctx, out, oshape, odt)
-        ctx._check(ctx._lib.ipa_remap_dev(ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
-                                          C.c_void_p(mapx.ptr.value + moff),
-                                          C.c_void_p(mapy.ptr.value + moff), mw, dst.ptr,
-                                          dtype_id(odt), dh, dw, dw, n, sh * sw, dh * dw, interp,
-                                          border, float(border_value)), 'remap')
-        return dst
-    if map_roi is not None:
-        raise ValueError('map_roi needs device arrays')
-    ctx = ctx or default_context()
-    src = _host(src)
-    mapx, mapy = _host(mapx, np.float32), _host(mapy, np.float32)
-    if mapx.shape != mapy.shape or mapx.ndim != 2:
-        raise ValueError('mapx/mapy must be 2-D and of equal shape')
-    n, sh, sw = as_frames(src)
-    dh, dw = mapx.shape
-    odt = _out_dtype(src.dtype, out_dtype)
-    dst = np.empty((dh, dw) if src.ndim == 2 else (n, dh, dw), odt)
-    ctx._check(ctx._lib.ipa_remap(ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, _p(mapx),
-                                  _p(mapy), _p(dst), dtype_id(odt), dh, dw, n, interp, border,
-                                  float(border_value)), 'remap')
-    return dst
+        coords = (C.c_void_p(mapx.ptr.value + moff), C.c_void_p(mapy.ptr.value + moff), mw)
+    else:
+        if map_roi is not None:
+            raise ValueError('map_roi needs device arrays')
+        ctx = ctx or default_context()
+        mapx, mapy = _host(mapx, np.float32), _host(mapy, np.float32)
+        if mapx.shape != mapy.shape or mapx.ndim != 2:
+            raise ValueError('mapx/mapy must be 2-D and of equal shape')
+        dh, dw = mapx.shape
+        coords = (_p(mapx), _p(mapy))
+    return _geometry('remap', src, coords, (dh, dw), interpolation, border_mode, border_value,
+                     out_dtype, out, ctx)
 
 
 def undistort(src, K, dist5, newK=None, interpolation='linear', border_mode='constant',
               border_value=0.0, out_dtype=None, out_shape=None, out=None, ctx=None):
     """LensDistortion.correct without map arrays (analytic coordinates)"""
-    interp, border = interp_id(interpolation), border_id(border_mode)
-    if newK is None:
-        newK = K
-    Kc, dc, nKc = L.dbl(np.ravel(K), 9), L.dbl(np.ravel(dist5)[:5], 5), L.dbl(np.ravel(newK), 9)
-    dev = _is_dev(src)
-    ctx = _ctx_of(src, ctx=ctx)
-    if not dev:
-        src = _host(src)
-    n, sh, sw = as_frames(src)
-    dh, dw = out_shape or (sh, sw)
-    odt = _out_dtype(src.dtype, out_dtype)
-    oshape = (dh, dw) if len(src.shape) == 2 else (n, dh, dw)
-    if dev:
-        dst = _dev_out(ctx, out, oshape, odt)
-        ctx._check(ctx._lib.ipa_undistort_dev(ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
-                                              Kc, dc, nKc, dst.ptr, dtype_id(odt), dh, dw, dw, n,
-                                              sh * sw, dh * dw, interp, border,
-                                              float(border_value)), 'undistort')
-        return dst
-    dst = np.empty(oshape, odt)
-    ctx._check(ctx._lib.ipa_undistort(ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, Kc, dc,
-                                      nKc, _p(dst), dtype_id(odt), dh, dw, n, interp, border,
-                                      float(border_value)), 'undistort')
-    return dst
+    return _geometry('undistort', src, _lens(K, dist5, K if newK is None else newK), out_shape,
+                     interpolation, border_mode, border_value, out_dtype, out, ctx)
 
 
 def warp_perspective(src, M_dst2src, out_shape, interpolation='linear', border_mode='constant',
                      border_value=0.0, out_dtype=None, out=None, ctx=None):
     """cv2.warpPerspective with M the DESTINATION->SOURCE matrix (pass inv(H)
     for a plain call, H for WARP_INVERSE_MAP)"""
-    interp, border = interp_id(interpolation), border_id(border_mode)
-    M = L.dbl(np.ravel(np.asarray(M_dst2src, dtype=np.float64)), 9)
-    dev = _is_dev(src)
-    ctx = _ctx_of(src, ctx=ctx)
-    if not dev:
-        src = _host(src)
-    n, sh, sw = as_frames(src)
-    dh, dw = int(out_shape[0]), int(out_shape[1])
-    odt = _out_dtype(src.dtype, out_dtype)
-    oshape = (dh, dw) if len(src.shape) == 2 else (n, dh, dw)
-    if dev:
-        dst = _dev_out(ctx, out, oshape, odt)
-        ctx._check(ctx._lib.ipa_warp_perspective_dev(ctx.handle, src.ptr, dtype_id(src.dtype), sh,
-                                                     sw, sw, M, dst.ptr, dtype_id(odt), dh, dw, dw,
-                                                     n, sh * sw, dh * dw, interp, border,
-                                                     float(border_value)), 'warp_perspective')
-        return dst
-    dst = np.empty(oshape, odt)
-    ctx._check(ctx._lib.ipa_warp_perspective(ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, M,
-                                             _p(dst), dtype_id(odt), dh, dw, n, interp, border,
-                                             float(border_value)), 'warp_perspective')
-    return dst
+    return _geometry('warp_perspective', src, (_mat3(M_dst2src),),
+                     (int(out_shape[0]), int(out_shape[1])), interpolation, border_mode,
+                     border_value, out_dtype, out, ctx)
 
 
 def _grid_cells(cell_rects, cell_M):
@@ -279,29 +300,10 @@ def warp_grid(src, cell_rects, cell_M, out_shape, interpolation='linear', border
     ``warp_perspective(src, cell_M[i], (h, w), ...)`` pasted there.  Rectangles come in paint
     order; where they overlap the last one wins.  Pixels no rectangle covers receive what a
     pixel wholly outside the source receives under 'constant' with border_value."""
-    interp, border = interp_id(interpolation), border_id(border_mode)
     rects, M, nc = _grid_cells(cell_rects, cell_M)
-    rp, mp = rects.ctypes.data_as(L._ip), M.ctypes.data_as(L._dp)
-    dev = _is_dev(src)
-    ctx = _ctx_of(src, ctx=ctx)
-    if not dev:
-        src = _host(src)
-    n, sh, sw = as_frames(src)
-    dh, dw = int(out_shape[0]), int(out_shape[1])
-    odt = _out_dtype(src.dtype, out_dtype)
-    oshape = (dh, dw) if len(src.shape) == 2 else (n, dh, dw)
-    if dev:
-        dst = _dev_out(ctx, out, oshape, odt)
-        ctx._check(ctx._lib.ipa_warp_grid_dev(ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
-                                              rp, mp, nc, dst.ptr, dtype_id(odt), dh, dw, dw, n,
-                                              sh * sw, dh * dw, interp, border,
-                                              float(border_value)), 'warp_grid')
-        return dst
-    dst = np.empty(oshape, odt)
-    ctx._check(ctx._lib.ipa_warp_grid(ctx.handle, _p(src), dtype_id(src.dtype), sh, sw, rp, mp, nc,
-                                      _p(dst), dtype_id(odt), dh, dw, n, interp, border,
-                                      float(border_value)), 'warp_grid')
-    return dst
+    return _geometry('warp_grid', src, (rects.ctypes.data_as(L._ip), _dptr(M), nc),
+                     (int(out_shape[0]), int(out_shape[1])), interpolation, border_mode,
+                     border_value, out_dtype, out, ctx)
 
 
 # --------------------------------------------------------------- filters --
@@ -325,7 +327,7 @@ def conv2d(img, kernel, mode='reflect', cval=0.0, mask=None, mode_y=None, out=No
     k = np.ascontiguousarray(kernel, dtype=np.float64)
     if k.ndim != 2:
         raise ValueError('kernel must be 2-D')
-    kp = k.ctypes.data_as(C.POINTER(C.c_double))
+    kp = _dptr(k)
     img = _float_img(img)
     ctx = _ctx_of(img, mask, ctx=ctx)
     n, h, w = as_frames(img)
@@ -359,21 +361,19 @@ def sepconv2d(img, ky, kx, mode='reflect', cval=0.0, out=None, ctx=None):
     b = border_id(mode)
     ky = np.zeros(0) if ky is None else np.ascontiguousarray(ky, dtype=np.float64).ravel()
     kx = np.zeros(0) if kx is None else np.ascontiguousarray(kx, dtype=np.float64).ravel()
-    dp = C.POINTER(C.c_double)
+    taps = (_dptr(ky), ky.size, _dptr(kx), kx.size)
     img = _float_img(img)
     ctx = _ctx_of(img, ctx=ctx)
     n, h, w = as_frames(img)
     if _is_dev(img):
         dst = _dev_out(ctx, out, img.shape, img.dtype)
         ctx._check(ctx._lib.ipa_sepconv2d_dev(ctx.handle, img.ptr, dtype_id(img.dtype), h, w, w,
-                                              ky.ctypes.data_as(dp), ky.size, kx.ctypes.data_as(dp),
-                                              kx.size, dst.ptr, w, n, h * w, h * w, b, b,
+                                              *taps, dst.ptr, w, n, h * w, h * w, b, b,
                                               float(cval)), 'sepconv2d')
         return dst
     dst = np.empty_like(img)
-    ctx._check(ctx._lib.ipa_sepconv2d(ctx.handle, _p(img), dtype_id(img.dtype), h, w,
-                                      ky.ctypes.data_as(dp), ky.size, kx.ctypes.data_as(dp),
-                                      kx.size, _p(dst), n, b, b, float(cval)), 'sepconv2d')
+    ctx._check(ctx._lib.ipa_sepconv2d(ctx.handle, _p(img), dtype_id(img.dtype), h, w, *taps,
+                                      _p(dst), n, b, b, float(cval)), 'sepconv2d')
     return dst
 
 
@@ -395,32 +395,54 @@ def gaussian_filter(img, sigma, mode='reflect', cval=0.0, truncate=4.0, out=None
     return sepconv2d(img, ks[0], ks[1], mode, cval, out=out, ctx=ctx)
 
 
+_FLOATS = (np.float32, np.float64)
+
+
+def _stage_in(name, x, ctx, dtypes=None, host=None, others=(), ndims=(2,), bad_shape=ValueError):
+    """One image of a single-image op, host array or DeviceArray -> (dev, ctx, d_in, h, w).
+    A host array goes through `host` (which may refuse it; None: the op takes DeviceArrays
+    only) and up to the device.  `dtypes`: what the kernel takes (None: the library decides),
+    TypeError otherwise; `bad_shape`: what a wrong number of dimensions raises.  `others` may
+    be DeviceArrays too and must live on the same context."""
+    dev = _is_dev(x)
+    if not dev and host is None:
+        raise TypeError('%s needs a DeviceArray' % name)
+    ctx = _ctx_of(x, *others, ctx=ctx)
+    d_in = x if dev else ctx.to_device(host(x))
+    if dtypes is not None and d_in.dtype not in dtypes:
+        raise TypeError('%s needs %s arrays (got %s)'
+                        % (name, ' / '.join(np.dtype(t).name for t in dtypes), d_in.dtype))
+    if d_in.ndim not in ndims:
+        raise bad_shape('%s works on %s-D arrays (got shape %s)'
+                        % (name, ' / '.join(str(d) for d in ndims), d_in.shape))
+    return dev, ctx, d_in, d_in.shape[-2], d_in.shape[-1]
+
+
+def _stage_out(dev, d_out):
+    """the result as the input came: DeviceArray for a DeviceArray, numpy otherwise"""
+    return d_out if dev else d_out.get()
+
+
+def _nonzero_u8(a):
+    return np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+
+
 def extend_array(arr, kernelXY, modex='reflect', modey='reflect', ctx=None):
     """filters/_extendArrayForConvolution.py:5-97 on the device"""
     kx, ky = int(kernelXY[0]), int(kernelXY[1])
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, ctx=ctx)
-    d_in = arr if dev else ctx.to_device(_host(arr))
-    if d_in.ndim != 2:
-        raise ValueError('extend_array works on 2-D arrays')
-    h, w = d_in.shape
+    dev, ctx, d_in, h, w = _stage_in('extend_array', arr, ctx, host=_host)
     oshape = (h + 2 * (ky // 2), w + 2 * (kx // 2))
     d_out = DeviceArray(ctx, oshape, d_in.dtype)
     ctx._check(ctx._lib.ipa_extend_array_dev(ctx.handle, d_in.ptr, dtype_id(d_in.dtype), h, w, w,
                                              kx, ky, border_id(modex), border_id(modey), d_out.ptr,
                                              oshape[1]), 'extend_array')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def conv_ydep(arr, kernels, modex='wrap', modey='reflect', ctx=None):
     """row-dependent k0 x k1 correlation, NaN-skipping
     (filters/varYSizeGaussianFilter.py:53-68); kernels: (H, k0, k1) float64"""
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, ctx=ctx)
-    d_in = arr if dev else ctx.to_device(_float_img(arr))
-    if d_in.ndim != 2:
-        raise ValueError('conv_ydep works on 2-D arrays')
-    h, w = d_in.shape
+    dev, ctx, d_in, h, w = _stage_in('conv_ydep', arr, ctx, host=_float_img)
     k = np.ascontiguousarray(kernels, dtype=np.float64)
     if k.ndim != 3 or k.shape[0] != h:
         raise ValueError('kernels must be (H, k0, k1)')
@@ -431,43 +453,40 @@ def conv_ydep(arr, kernels, modex='wrap', modey='reflect', ctx=None):
                                           border_id(modey), d_out.ptr, w), 'conv_ydep')
     if dev:
         d_out._keepalive = d_k  # the table must outlive the asynchronous launch
-        return d_out
-    return d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def var_y_gauss(arr, sig_min, sig_max, ky, rowk, modex='wrap', modey='reflect', ctx=None):
     """filters/varYSizeGaussianFilter.py:9-68 in one launch pair: per-row Gaussian tables built
     on the device (stdys = linspace(sig_min, sig_max, H)), `rowk` = the kx x-responses"""
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, ctx=ctx)
-    d_in = arr if dev else ctx.to_device(_float_img(arr))
-    if d_in.ndim != 2:
-        raise ValueError('var_y_gauss works on 2-D arrays')
-    h, w = d_in.shape
+    dev, ctx, d_in, h, w = _stage_in('var_y_gauss', arr, ctx, host=_float_img)
     rk = np.ascontiguousarray(rowk, dtype=np.float64).ravel()
     d_out = DeviceArray(ctx, (h, w), d_in.dtype)
     ctx._check(ctx._lib.ipa_var_y_gauss_dev(
         ctx.handle, d_in.ptr, dtype_id(d_in.dtype), h, w, w, float(sig_min), float(sig_max),
-        int(ky), rk.ctypes.data_as(C.POINTER(C.c_double)), rk.size, border_id(modex),
-        border_id(modey), d_out.ptr, w), 'var_y_gauss')
-    return d_out if dev else d_out.get()
+        int(ky), _dptr(rk), rk.size, border_id(modex), border_id(modey), d_out.ptr, w),
+        'var_y_gauss')
+    return _stage_out(dev, d_out)
 
 
 def local_std(img, blurred, ksize, ctx=None):
     """filters/standardDeviation.py:34-70 (_calc) for ksize=(kx, ky)"""
-    dev = _is_dev(img)
-    ctx = _ctx_of(img, blurred, ctx=ctx)
-    d_img = img if dev else ctx.to_device(_float_img(img))
+    dev, ctx, d_img, h, w = _stage_in('local_std', img, ctx, host=_float_img, others=(blurred,))
     d_bl = blurred if _is_dev(blurred) else ctx.to_device(
         np.ascontiguousarray(blurred, dtype=d_img.dtype))
-    if d_img.ndim != 2 or d_bl.shape != d_img.shape or d_bl.dtype != d_img.dtype:
+    if d_bl.shape != d_img.shape or d_bl.dtype != d_img.dtype:
         raise ValueError('img and blurred must be 2-D arrays of equal shape and dtype')
-    h, w = d_img.shape
     d_out = DeviceArray(ctx, (h, w), d_img.dtype)
     ctx._check(ctx._lib.ipa_local_std_dev(ctx.handle, d_img.ptr, d_bl.ptr, dtype_id(d_img.dtype),
                                           h, w, w, w, int(ksize[0]), int(ksize[1]), d_out.ptr, w),
                'local_std')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
+
+
+def _float_ndarray(a):
+    if not (isinstance(a, np.ndarray) and a.dtype in _FLOATS):
+        raise TypeError('masked_mean needs a float32/float64 ndarray')
+    return np.ascontiguousarray(a)
 
 
 def masked_mean(arr, mask, ksize, fill_mask=True, ctx=None, fn='median'):
@@ -475,80 +494,50 @@ def masked_mean(arr, mask, ksize, fill_mask=True, ctx=None, fn='median'):
     other than 'mean': median, as in the reference).  fill_mask=True fills ``arr`` IN PLACE (host
     arrays are copied back into ``arr``); fill_mask=False returns a new NaN-padded array."""
     fn = 'mean' if fn == 'mean' else 'median'
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, mask, ctx=ctx)
-    if dev:
-        if not _is_dev(mask):
-            raise TypeError('device array needs a device mask')
-        d_arr, d_mask = arr, mask
-        if d_arr.dtype not in (np.float32, np.float64):
-            raise TypeError('masked_mean needs float32/float64 arrays')
-    else:
-        if not (isinstance(arr, np.ndarray) and arr.dtype in (np.float32, np.float64)):
-            raise TypeError('masked_mean needs a float32/float64 ndarray')
-        d_arr = ctx.to_device(np.ascontiguousarray(arr))
-        d_mask = ctx.to_device(np.ascontiguousarray(mask, dtype=np.uint8))
-    if d_arr.ndim != 2 or tuple(d_mask.shape) != tuple(d_arr.shape) or d_mask.dtype != np.uint8:
+    if _is_dev(arr) and not _is_dev(mask):
+        raise TypeError('device array needs a device mask')
+    dev, ctx, d_arr, h, w = _stage_in('masked_mean', arr, ctx, _FLOATS, _float_ndarray, (mask,))
+    d_mask = mask if dev else ctx.to_device(np.ascontiguousarray(mask, dtype=np.uint8))
+    if tuple(d_mask.shape) != tuple(d_arr.shape) or d_mask.dtype != np.uint8:
         raise ValueError('arr and mask must be 2-D arrays of equal shape (mask uint8/bool)')
-    h, w = d_arr.shape
     d_out = d_arr if fill_mask else DeviceArray(ctx, (h, w), d_arr.dtype)
     f = ctx._lib.ipa_masked_mean_dev if fn == 'mean' else ctx._lib.ipa_masked_median_dev
     ctx._check(f(ctx.handle, d_arr.ptr, dtype_id(d_arr.dtype), d_mask.ptr, h, w, w, w, int(ksize),
                  int(bool(fill_mask)), d_out.ptr, w), 'masked_' + fn)
-    if dev:
-        return d_out
-    if fill_mask:
+    if fill_mask and not dev:
         arr[...] = d_out.get()
         return arr
-    return d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def nan_max(arr, ksize, ctx=None):
     """filters/nan_maximum_filter.py:17-37"""
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, ctx=ctx)
-    d_arr = arr if dev else ctx.to_device(_float_img(arr))
-    if d_arr.ndim != 2 or d_arr.dtype not in (np.float32, np.float64):
-        raise TypeError('nan_max needs a 2-D float32/float64 array')
-    h, w = d_arr.shape
+    dev, ctx, d_arr, h, w = _stage_in('nan_max', arr, ctx, _FLOATS, _float_img, bad_shape=TypeError)
     d_out = DeviceArray(ctx, (h, w), d_arr.dtype)
     ctx._check(ctx._lib.ipa_nan_max_dev(ctx.handle, d_arr.ptr, dtype_id(d_arr.dtype), h, w, w,
                                         int(ksize), d_out.ptr, w), 'nan_max')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def closest_distance(arr, ksize=30, dtype=np.uint16, ctx=None):
-    """render/closestDirectDistance.py:17-41: distance to the closest non-zero pixel"""
+    """render/closestDirectDistance.py:17-41: distance to the closest non-zero pixel (device
+    input: uint8, non-zero = set)"""
     dtype = np.dtype(dtype)
     if dtype not in (np.uint16, np.float64):
         raise NotImplementedError('closest_distance writes uint16 or float64')
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, ctx=ctx)
-    if dev:
-        if arr.dtype != np.uint8:
-            raise TypeError('device input must be uint8 (non-zero = set)')
-        d_arr = arr
-    else:
-        d_arr = ctx.to_device(np.ascontiguousarray(np.asarray(arr) != 0, dtype=np.uint8))
-    if d_arr.ndim != 2:
-        raise ValueError('closest_distance works on 2-D arrays')
-    h, w = d_arr.shape
+    dev, ctx, d_arr, h, w = _stage_in('closest_distance', arr, ctx, (np.uint8,), _nonzero_u8)
     d_out = DeviceArray(ctx, (h, w), dtype)
     ctx._check(ctx._lib.ipa_closest_distance_dev(ctx.handle, d_arr.ptr, h, w, w, int(ksize),
                                                  d_out.ptr, dtype_id(dtype), w), 'closest_distance')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def pos_intensity_unc(image, sx, sy, ksize, ctx=None):
     """uncertainty/positionToIntensityUncertainty.py:7-49; ksize = half window.  sx / sy are
     both scalars or both (H, W) maps; returns float64"""
     maps = isinstance(sx, (np.ndarray, DeviceArray))
-    dev = _is_dev(image)
-    ctx = _ctx_of(image, sx if _is_dev(sx) else None, sy if _is_dev(sy) else None, ctx=ctx)
-    d_img = image if dev else ctx.to_device(_float_img(image))
-    if d_img.ndim != 2 or d_img.dtype not in (np.float32, np.float64):
-        raise TypeError('pos_intensity_unc needs a 2-D float32/float64 image')
-    h, w = d_img.shape
+    dev, ctx, d_img, h, w = _stage_in('pos_intensity_unc', image, ctx, _FLOATS, _float_img,
+                                      (sx, sy), bad_shape=TypeError)
     d_sx = d_sy = None
     if maps:
         d_sx = sx if _is_dev(sx) else ctx.to_device(np.ascontiguousarray(sx, dtype=np.float64))
@@ -562,19 +551,15 @@ def pos_intensity_unc(image, sx, sy, ksize, ctx=None):
         d_sx.ptr if maps else None, d_sy.ptr if maps else None, w,
         0.0 if maps else float(sx), 0.0 if maps else float(sy), int(ksize), d_out.ptr, w),
         'pos_intensity_unc')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def median_threshold(img, threshold=0.1, condition='>', want_indices=True, ctx=None, size=3):
     """filters/medianThreshold.py:7-30: -> (out, indices) new arrays"""
     if condition not in ('>', '<'):
         raise ValueError("condition must be '>' or '<'")
-    dev = _is_dev(img)
-    ctx = _ctx_of(img, ctx=ctx)
-    d_img = img if dev else ctx.to_device(_float_img(img))
-    if d_img.ndim != 2 or d_img.dtype not in (np.float32, np.float64):
-        raise TypeError('median_threshold needs a 2-D float32/float64 array')
-    h, w = d_img.shape
+    dev, ctx, d_img, h, w = _stage_in('median_threshold', img, ctx, _FLOATS, _float_img,
+                                      bad_shape=TypeError)
     d_out = DeviceArray(ctx, (h, w), d_img.dtype)
     d_idx = DeviceArray(ctx, (h, w), np.uint8) if want_indices else None
     size = int(size)
@@ -593,12 +578,8 @@ def calib_prefilter(img, bg=None, ff=None, threshold=0.1, out=None, ctx=None):
     """stages 2-4 of CameraCalibration.correct (camera/CameraCalibration.py:416-437) in one
     kernel: dark current, flat field, nan_to_num + thresholded 3x3 median.  bg / ff are cast to
     the image dtype; returns a new array (DeviceArray for device input)."""
-    dev = _is_dev(img)
-    ctx = _ctx_of(img, bg, ff, ctx=ctx)
-    d_img = img if dev else ctx.to_device(_float_img(img))
-    if d_img.ndim != 2 or d_img.dtype not in (np.float32, np.float64):
-        raise TypeError('calib_prefilter needs a 2-D float32/float64 array')
-    h, w = d_img.shape
+    dev, ctx, d_img, h, w = _stage_in('calib_prefilter', img, ctx, _FLOATS, _float_img, (bg, ff),
+                                      bad_shape=TypeError)
 
     def side(a, name):
         if a is None:
@@ -618,7 +599,7 @@ def calib_prefilter(img, bg=None, ff=None, threshold=0.1, out=None, ctx=None):
         ctx.handle, d_img.ptr, dtype_id(d_img.dtype), d_bg.ptr if d_bg is not None else None,
         d_ff.ptr if d_ff is not None else None, h, w, w, w, w, float(threshold), d_out.ptr, w),
         'calib_prefilter')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 # ------------------------------------------------- single-time effects --
@@ -683,18 +664,8 @@ def remove_single_pixels(arr, out=None, ctx=None):
     """filters/removeSinglePixels.py:4-30, not in place: a set pixel stays set only when one of
     its <= 8 in-image neighbours is set.  Host input (any dtype, non-zero = set) gives a bool
     array, a (h, w) uint8 DeviceArray gives a uint8 DeviceArray."""
-    dev = _is_dev(arr)
-    ctx = _ctx_of(arr, out, ctx=ctx)
-    if dev:
-        if arr.dtype != np.uint8 or arr.ndim != 2:
-            raise TypeError('remove_single_pixels needs a 2-D uint8 DeviceArray')
-        d = arr
-    else:
-        a = np.asarray(arr)
-        if a.ndim != 2:
-            raise TypeError('remove_single_pixels needs a 2-D array')
-        d = ctx.to_device(np.ascontiguousarray(a != 0, dtype=np.uint8))
-    h, w = d.shape
+    dev, ctx, d, h, w = _stage_in('remove_single_pixels', arr, ctx, (np.uint8,), _nonzero_u8,
+                                  (out,), bad_shape=TypeError)
     d_out = _dev_out(ctx, out, (h, w), np.uint8) if dev else DeviceArray(ctx, (h, w), np.uint8)
     ctx._check(ctx._lib.ipa_remove_single_pixels_dev(ctx.handle, d.ptr, h, w, w, d_out.ptr, w),
                'remove_single_pixels')
@@ -735,184 +706,135 @@ def nl_means(img, patch_size=7, patch_distance=11, h=0.1, sigma=0.0, out=None, c
                          % (tuple(img.shape),))
     if out is not None and (not dev or out is img):
         raise ValueError('nl_means: out must be a DeviceArray other than the (device) source')
-    ctx = _ctx_of(img, out, ctx=ctx)
-    d = img if dev else ctx.to_device(np.ascontiguousarray(img))
-    n, hh, ww = as_frames(d)
+    dev, ctx, d, hh, ww = _stage_in('nl_means', img, ctx, _FLOATS, np.ascontiguousarray, (out,),
+                                    ndims=(2, 3))
+    n = as_frames(d)[0]
     d_out = _dev_out(ctx, out, d.shape, d.dtype)
     ctx._check(ctx._lib.ipa_nl_means_dev(
         ctx.handle, d.ptr, dtype_id(d.dtype), n, hh, ww, ww, hh * ww, patch_size, patch_distance, h,
         sigma, d_out.ptr, ww, hh * ww), 'nl_means')
-    return d_out if dev else d_out.get()
+    return _stage_out(dev, d_out)
 
 
 def nan_to_zero(img):
     """img[isnan(img)] = 0 in place on a float32 / float64 DeviceArray, (h, w) or (n, h, w)
     (ipa_nan_to_zero_dev; camera/CameraCalibration.py:467).  Returns img."""
-    if not _is_dev(img) or img.dtype not in (np.float32, np.float64):
-        raise TypeError('nan_to_zero needs a float32 / float64 DeviceArray')
-    n, hh, ww = as_frames(img)
-    img.ctx._check(img.ctx._lib.ipa_nan_to_zero_dev(img.ctx.handle, img.ptr, dtype_id(img.dtype), n, hh,
-                                                    ww, ww, hh * ww), 'nan_to_zero')
+    _, ctx, _, hh, ww = _stage_in('nan_to_zero', img, None, _FLOATS, ndims=(2, 3))
+    ctx._check(ctx._lib.ipa_nan_to_zero_dev(ctx.handle, img.ptr, dtype_id(img.dtype),
+                                            as_frames(img)[0], hh, ww, ww, hh * ww), 'nan_to_zero')
     return img
 
 
 # ------------------------------------------------- fused remap -> filter --
-def _fused_out(ctx, src, out, dh, dw, n):
-    odt = np.float64 if src.dtype == np.float64 else np.float32
-    return _dev_out(ctx, out, (dh, dw) if src.ndim == 2 else (n, dh, dw), odt), odt
-
-
 def remap_conv2d(src, mapx, mapy, kernel, interpolation='linear', border_mode='constant',
                  border_value=0.0, conv_mode='reflect', out=None, ctx=None):
     """remap followed by a K x K centred correlation, one kernel, device arrays only"""
-    ctx = _ctx_of(src, mapx, mapy, ctx=ctx)
-    if not (_is_dev(src) and _is_dev(mapx) and _is_dev(mapy)):
-        raise TypeError('remap_conv2d works on DeviceArrays (use Context.to_device)')
+    ctx = _dev_only('remap_conv2d', ctx, src, mapx, mapy)
     _check_dev_maps(mapx, mapy)
-    k = np.ascontiguousarray(kernel, dtype=np.float64)
-    n, sh, sw = as_frames(src)
-    dh, dw = mapx.shape
-    dst, odt = _fused_out(ctx, src, out, dh, dw, n)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_remap_conv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw, mapx.ptr, mapy.ptr, dw,
-        k.ctypes.data_as(C.POINTER(C.c_double)), k.shape[0], k.shape[1], dst.ptr, dtype_id(odt),
-        dh, dw, dw, n, sh * sw, dh * dw, interp_id(interpolation), border_id(border_mode),
-        float(border_value), cb, cb), 'remap_conv2d')
-    return dst
+    return _geometry('remap_conv2d', src, (mapx.ptr, mapy.ptr, mapx.shape[1]), mapx.shape,
+                     interpolation, border_mode, border_value, None, out, ctx,
+                     _dense_filt(kernel, conv_mode))
 
 
 def undistort_conv2d(src, K, dist5, newK, kernel, interpolation='linear', border_mode='constant',
                      border_value=0.0, conv_mode='reflect', out_shape=None, out=None, ctx=None):
-    ctx = _ctx_of(src, ctx=ctx)
-    if not _is_dev(src):
-        raise TypeError('undistort_conv2d works on DeviceArrays (use Context.to_device)')
-    if newK is None:
-        newK = K
-    k = np.ascontiguousarray(kernel, dtype=np.float64)
-    n, sh, sw = as_frames(src)
-    dh, dw = out_shape or (sh, sw)
-    dst, odt = _fused_out(ctx, src, out, dh, dw, n)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_undistort_conv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw, L.dbl(np.ravel(K), 9),
-        L.dbl(np.ravel(dist5)[:5], 5), L.dbl(np.ravel(newK), 9),
-        k.ctypes.data_as(C.POINTER(C.c_double)), k.shape[0], k.shape[1], dst.ptr, dtype_id(odt),
-        dh, dw, dw, n, sh * sw, dh * dw, interp_id(interpolation), border_id(border_mode),
-        float(border_value), cb, cb), 'undistort_conv2d')
-    return dst
+    ctx = _dev_only('undistort_conv2d', ctx, src)
+    return _geometry('undistort_conv2d', src, _lens(K, dist5, K if newK is None else newK),
+                     out_shape, interpolation, border_mode, border_value, None, out, ctx,
+                     _dense_filt(kernel, conv_mode))
 
 
 def warp_perspective_conv2d(src, M_dst2src, out_shape, kernel, interpolation='linear',
                             border_mode='constant', border_value=0.0, conv_mode='reflect',
                             out=None, ctx=None):
-    ctx = _ctx_of(src, ctx=ctx)
-    if not _is_dev(src):
-        raise TypeError('warp_perspective_conv2d works on DeviceArrays (use Context.to_device)')
-    k = np.ascontiguousarray(kernel, dtype=np.float64)
-    n, sh, sw = as_frames(src)
-    dh, dw = int(out_shape[0]), int(out_shape[1])
-    dst, odt = _fused_out(ctx, src, out, dh, dw, n)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_warp_perspective_conv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
-        L.dbl(np.ravel(np.asarray(M_dst2src, dtype=np.float64)), 9),
-        k.ctypes.data_as(C.POINTER(C.c_double)), k.shape[0], k.shape[1], dst.ptr, dtype_id(odt),
-        dh, dw, dw, n, sh * sw, dh * dw, interp_id(interpolation), border_id(border_mode),
-        float(border_value), cb, cb), 'warp_perspective_conv2d')
-    return dst
-
-
-def _sep_taps(ky, kx):
-    ky = np.ascontiguousarray(ky, dtype=np.float64).ravel()
-    kx = np.ascontiguousarray(kx, dtype=np.float64).ravel()
-    dp = C.POINTER(C.c_double)
-    return ky, kx, ky.ctypes.data_as(dp), kx.ctypes.data_as(dp)
+    ctx = _dev_only('warp_perspective_conv2d', ctx, src)
+    return _geometry('warp_perspective_conv2d', src, (_mat3(M_dst2src),),
+                     (int(out_shape[0]), int(out_shape[1])), interpolation, border_mode,
+                     border_value, None, out, ctx, _dense_filt(kernel, conv_mode))
 
 
 def remap_sepconv2d(src, mapx, mapy, ky, kx, interpolation='linear', border_mode='constant',
                     border_value=0.0, conv_mode='reflect', out=None, ctx=None):
     """remap followed by a separable correlation (axis 0 with ky, then axis 1 with kx; the
     scipy.ndimage.gaussian_filter order) — one kernel where built, device arrays only"""
-    ctx = _ctx_of(src, mapx, mapy, ctx=ctx)
-    if not (_is_dev(src) and _is_dev(mapx) and _is_dev(mapy)):
-        raise TypeError('remap_sepconv2d works on DeviceArrays (use Context.to_device)')
+    ctx = _dev_only('remap_sepconv2d', ctx, src, mapx, mapy)
     _check_dev_maps(mapx, mapy)
-    ky, kx, pky, pkx = _sep_taps(ky, kx)
-    n, sh, sw = as_frames(src)
-    dh, dw = mapx.shape
-    dst = _dev_out(ctx, out, (dh, dw) if src.ndim == 2 else (n, dh, dw), np.float32)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_remap_sepconv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw, mapx.ptr, mapy.ptr, dw, pky, ky.size,
-        pkx, kx.size, dst.ptr, dtype_id(np.float32), dh, dw, dw, n, sh * sw, dh * dw,
-        interp_id(interpolation), border_id(border_mode), float(border_value), cb, cb),
-        'remap_sepconv2d')
-    return dst
+    return _geometry('remap_sepconv2d', src, (mapx.ptr, mapy.ptr, mapx.shape[1]), mapx.shape,
+                     interpolation, border_mode, border_value, None, out, ctx,
+                     _sep_filt(ky, kx, conv_mode))
 
 
 def undistort_sepconv2d(src, K, dist5, newK, ky, kx, interpolation='linear',
                         border_mode='constant', border_value=0.0, conv_mode='reflect',
                         out_shape=None, out=None, ctx=None):
-    ctx = _ctx_of(src, ctx=ctx)
-    if not _is_dev(src):
-        raise TypeError('undistort_sepconv2d works on DeviceArrays (use Context.to_device)')
-    if newK is None:
-        newK = K
-    ky, kx, pky, pkx = _sep_taps(ky, kx)
-    n, sh, sw = as_frames(src)
-    dh, dw = out_shape or (sh, sw)
-    dst = _dev_out(ctx, out, (dh, dw) if src.ndim == 2 else (n, dh, dw), np.float32)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_undistort_sepconv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw, L.dbl(np.ravel(K), 9),
-        L.dbl(np.ravel(dist5)[:5], 5), L.dbl(np.ravel(newK), 9), pky, ky.size, pkx, kx.size,
-        dst.ptr, dtype_id(np.float32), dh, dw, dw, n, sh * sw, dh * dw, interp_id(interpolation),
-        border_id(border_mode), float(border_value), cb, cb), 'undistort_sepconv2d')
-    return dst
+    ctx = _dev_only('undistort_sepconv2d', ctx, src)
+    return _geometry('undistort_sepconv2d', src, _lens(K, dist5, K if newK is None else newK),
+                     out_shape, interpolation, border_mode, border_value, None, out, ctx,
+                     _sep_filt(ky, kx, conv_mode))
 
 
 def warp_perspective_sepconv2d(src, M_dst2src, out_shape, ky, kx, interpolation='linear',
                                border_mode='constant', border_value=0.0, conv_mode='reflect',
                                out=None, ctx=None):
-    ctx = _ctx_of(src, ctx=ctx)
-    if not _is_dev(src):
-        raise TypeError('warp_perspective_sepconv2d works on DeviceArrays (use Context.to_device)')
-    ky, kx, pky, pkx = _sep_taps(ky, kx)
-    n, sh, sw = as_frames(src)
-    dh, dw = int(out_shape[0]), int(out_shape[1])
-    dst = _dev_out(ctx, out, (dh, dw) if src.ndim == 2 else (n, dh, dw), np.float32)
-    cb = border_id(conv_mode)
-    ctx._check(ctx._lib.ipa_warp_perspective_sepconv2d_dev(
-        ctx.handle, src.ptr, dtype_id(src.dtype), sh, sw, sw,
-        L.dbl(np.ravel(np.asarray(M_dst2src, dtype=np.float64)), 9), pky, ky.size, pkx, kx.size,
-        dst.ptr, dtype_id(np.float32), dh, dw, dw, n, sh * sw, dh * dw, interp_id(interpolation),
-        border_id(border_mode), float(border_value), cb, cb), 'warp_perspective_sepconv2d')
-    return dst
+    ctx = _dev_only('warp_perspective_sepconv2d', ctx, src)
+    return _geometry('warp_perspective_sepconv2d', src, (_mat3(M_dst2src),),
+                     (int(out_shape[0]), int(out_shape[1])), interpolation, border_mode,
+                     border_value, None, out, ctx, _sep_filt(ky, kx, conv_mode))
 
 
 # ------------------------------------------------------------------- IDW --
+def _fill(name, grid, mask, args, ctx, masked=True, any_dtype=False, mask_written=False):
+    """The in-place fills: ipa_<name>_dev on a DeviceArray grid, the host-pointer ipa_<name> on
+    an ndarray, either with (grid, dtype[, mask], h, w[, pitch]) and then the fill's own `args`.
+    `masked` False: the fill takes no mask.  The library reads h * w mask bytes, so a mask of any other
+    shape is refused here (ValueError), on the host and on the device.  A host grid is written
+    where it lies and must be a C-contiguous 2-D ndarray, float32 / float64 unless `any_dtype`;
+    `mask_written`: so is the mask, bool / uint8."""
+    ctx = _ctx_of(grid, mask, ctx=ctx)
+    if _is_dev(grid):
+        if grid.ndim != 2:
+            raise ValueError('grid must be 2-D')
+        m = ()
+        if masked:
+            if not _is_dev(mask):
+                raise TypeError('device grid needs a device mask')
+            if mask.dtype != np.uint8 or tuple(mask.shape) != tuple(grid.shape):
+                raise ValueError('device mask must be uint8 of shape %s (got %s %s)'
+                                 % (grid.shape, mask.dtype, mask.shape))
+            m = (mask.ptr,)
+        h, w = grid.shape
+        status = getattr(ctx._lib, 'ipa_%s_dev' % name)(
+            ctx.handle, grid.ptr, dtype_id(grid.dtype), *m, h, w, w, *args)
+    else:
+        if not (isinstance(grid, np.ndarray) and grid.flags.c_contiguous and grid.ndim == 2):
+            raise ValueError('grid must be a C-contiguous 2-D ndarray (it is modified in place)')
+        if not any_dtype and grid.dtype not in _FLOATS:
+            raise TypeError('grid must be float32 or float64')
+        m = ()
+        if mask_written:
+            if not (isinstance(mask, np.ndarray) and mask.flags.c_contiguous and
+                    mask.shape == grid.shape and mask.dtype in (np.bool_, np.uint8)):
+                raise ValueError('mask must be a C-contiguous bool / uint8 array of the grid\'s shape '
+                                 '(it is modified in place)')
+            m = (_p(mask.view(np.uint8)),)
+        elif masked:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != grid.shape:
+                raise ValueError('mask and grid differ in shape')
+            m = (_p(mask),)
+        h, w = grid.shape
+        status = getattr(ctx._lib, 'ipa_%s' % name)(
+            ctx.handle, _p(grid), dtype_id(grid.dtype), *m, h, w, *args)
+    ctx._check(status, name)
+    return grid
+
+
 def idw_fill(grid, mask, ksize, weights, ctx=None):
     """in-place IDW hole filling (interpolate2dStructuredIDW._calc)"""
     w = np.ascontiguousarray(weights, dtype=np.float64)
     if w.shape != (2 * ksize + 1, 2 * ksize + 1):
         raise ValueError('weights must be (2*ksize+1)^2')
-    wp = w.ctypes.data_as(C.POINTER(C.c_double))
-    ctx = _ctx_of(grid, mask, ctx=ctx)
-    if _is_dev(grid):
-        if not _is_dev(mask):
-            raise TypeError('device grid needs a device mask')
-        h, wd = grid.shape
-        ctx._check(ctx._lib.ipa_idw_fill_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype), mask.ptr,
-                                             h, wd, wd, int(ksize), wp), 'idw_fill')
-        return grid
-    if not (isinstance(grid, np.ndarray) and grid.flags.c_contiguous and grid.ndim == 2):
-        raise ValueError('grid must be a C-contiguous 2-D ndarray (it is modified in place)')
-    m = np.ascontiguousarray(mask, dtype=np.uint8)
-    h, wd = grid.shape
-    ctx._check(ctx._lib.ipa_idw_fill(ctx.handle, _p(grid), dtype_id(grid.dtype), _p(m), h, wd,
-                                     int(ksize), wp), 'idw_fill')
-    return grid
+    return _fill('idw_fill', grid, mask, (int(ksize), _dptr(w)), ctx, any_dtype=True)
 
 
 def fast_idw_fill(grid, mask, offsets, weights, minnvals, ctx=None):
@@ -922,31 +844,8 @@ def fast_idw_fill(grid, mask, offsets, weights, minnvals, ctx=None):
     n = int(w.size)
     if offs.shape != (n, 2):
         raise ValueError('offsets must be (n,2) matching weights')
-    wp = w.ctypes.data_as(C.POINTER(C.c_double))
-    ctx = _ctx_of(grid, mask, ctx=ctx)
-    if _is_dev(grid):
-        if not _is_dev(mask):
-            raise TypeError('device grid needs a device mask')
-        h, wd = grid.shape
-        ctx._check(ctx._lib.ipa_fast_idw_fill_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype),
-                                                  mask.ptr, h, wd, wd, _p(offs), wp, n,
-                                                  int(minnvals)), 'fast_idw_fill')
-        return grid
-    if not (isinstance(grid, np.ndarray) and grid.flags.c_contiguous and grid.ndim == 2):
-        raise ValueError('grid must be a C-contiguous 2-D ndarray (it is modified in place)')
-    m = np.ascontiguousarray(mask, dtype=np.uint8)
-    h, wd = grid.shape
-    ctx._check(ctx._lib.ipa_fast_idw_fill(ctx.handle, _p(grid), dtype_id(grid.dtype), _p(m), h,
-                                          wd, _p(offs), wp, n, int(minnvals)), 'fast_idw_fill')
-    return grid
-
-
-def _fill_grid(grid):
-    if not (isinstance(grid, np.ndarray) and grid.flags.c_contiguous and grid.ndim == 2):
-        raise ValueError('grid must be a C-contiguous 2-D ndarray (it is modified in place)')
-    if grid.dtype not in (np.float32, np.float64):
-        raise TypeError('grid must be float32 or float64')
-    return grid.shape
+    return _fill('fast_idw_fill', grid, mask, (_p(offs), _dptr(w), n, int(minnvals)),
+                 ctx, any_dtype=True)
 
 
 def unstructured_idw(x, y, v, grid, power=2, ctx=None):
@@ -954,91 +853,35 @@ def unstructured_idw(x, y, v, grid, power=2, ctx=None):
     xs, ys, vs = (np.ascontiguousarray(np.ravel(a), dtype=np.float64) for a in (x, y, v))
     if not (xs.size == ys.size == vs.size and vs.size >= 1):
         raise ValueError('x, y, v must be 1-D, of equal length >= 1')
-    dp = C.POINTER(C.c_double)
-    px, py, pv = (a.ctypes.data_as(dp) for a in (xs, ys, vs))
-    ctx = _ctx_of(grid, ctx=ctx)
-    if _is_dev(grid):
-        h, w = grid.shape
-        ctx._check(ctx._lib.ipa_unstructured_idw_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype), h,
-                                                     w, w, px, py, pv, int(vs.size), float(power)),
-                   'unstructured_idw')
-        return grid
-    h, w = _fill_grid(grid)
-    ctx._check(ctx._lib.ipa_unstructured_idw(ctx.handle, _p(grid), dtype_id(grid.dtype), h, w, px,
-                                             py, pv, int(vs.size), float(power)),
-               'unstructured_idw')
-    return grid
+    return _fill('unstructured_idw', grid, None,
+                 (_dptr(xs), _dptr(ys), _dptr(vs), int(vs.size), float(power)), ctx, masked=False)
 
 
 def circular_idw_fill(grid, mask, ksize, power=2, fr=1, fphi=1, cx=0, cy=0, ctx=None):
     """in-place IDW hole filling with polar distances (interpolateCircular2dStructuredIDW)"""
-    ctx = _ctx_of(grid, mask, ctx=ctx)
-    args = (int(ksize), float(power), float(fr), float(fphi), float(cx), float(cy))
-    if _is_dev(grid):
-        if not _is_dev(mask):
-            raise TypeError('device grid needs a device mask')
-        h, w = grid.shape
-        ctx._check(ctx._lib.ipa_circular_idw_fill_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype),
-                                                      mask.ptr, h, w, w, *args),
-                   'circular_idw_fill')
-        return grid
-    h, w = _fill_grid(grid)
-    m = np.ascontiguousarray(mask, dtype=np.uint8)
-    if m.shape != grid.shape:
-        raise ValueError('mask and grid differ in shape')
-    ctx._check(ctx._lib.ipa_circular_idw_fill(ctx.handle, _p(grid), dtype_id(grid.dtype), _p(m), h,
-                                              w, *args), 'circular_idw_fill')
-    return grid
+    return _fill('circular_idw_fill', grid, mask,
+                 (int(ksize), float(power), float(fr), float(fphi), float(cx), float(cy)), ctx)
 
 
 def cross_avg_fill(grid, mask, ksize, power=2, ctx=None):
     """in-place fill of large holes from the four axis directions
     (interpolate2dStructuredCrossAvg)"""
-    ctx = _ctx_of(grid, mask, ctx=ctx)
-    if _is_dev(grid):
-        if not _is_dev(mask):
-            raise TypeError('device grid needs a device mask')
-        h, w = grid.shape
-        ctx._check(ctx._lib.ipa_cross_avg_fill_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype),
-                                                   mask.ptr, h, w, w, int(ksize), float(power)),
-                   'cross_avg_fill')
-        return grid
-    h, w = _fill_grid(grid)
-    m = np.ascontiguousarray(mask, dtype=np.uint8)
-    if m.shape != grid.shape:
-        raise ValueError('mask and grid differ in shape')
-    ctx._check(ctx._lib.ipa_cross_avg_fill(ctx.handle, _p(grid), dtype_id(grid.dtype), _p(m), h, w,
-                                           int(ksize), float(power)), 'cross_avg_fill')
-    return grid
+    return _fill('cross_avg_fill', grid, mask, (int(ksize), float(power)), ctx)
 
 
 def point_spread_idw(grid, mask, ksize, power=2, max_iter=1e5, ctx=None):
     """in-place point-spread IDW fill (interpolate2dStructuredPointSpreadIDW): grid AND mask are
     modified - filled pixels are unmasked"""
-    ctx = _ctx_of(grid, mask, ctx=ctx)
-    it = int(min(max_iter, 2 ** 62))
-    if _is_dev(grid):
-        if not _is_dev(mask):
-            raise TypeError('device grid needs a device mask')
-        h, w = grid.shape
-        ctx._check(ctx._lib.ipa_point_spread_idw_dev(ctx.handle, grid.ptr, dtype_id(grid.dtype),
-                                                     mask.ptr, h, w, w, int(ksize), float(power), it),
-                   'point_spread_idw')
-        return grid
-    h, w = _fill_grid(grid)
-    if not (isinstance(mask, np.ndarray) and mask.flags.c_contiguous and mask.shape == grid.shape and
-            mask.dtype in (np.bool_, np.uint8)):
-        raise ValueError('mask must be a C-contiguous bool / uint8 array of the grid\'s shape '
-                         '(it is modified in place)')
-    ctx._check(ctx._lib.ipa_point_spread_idw(ctx.handle, _p(grid), dtype_id(grid.dtype),
-                                             _p(mask.view(np.uint8)), h, w, int(ksize), float(power),
-                                             it), 'point_spread_idw')
-    return grid
+    return _fill('point_spread_idw', grid, mask,
+                 (int(ksize), float(power), int(min(max_iter, 2 ** 62))), ctx, mask_written=True)
 
 
 # ------------------------------------------------------- fastFilter / fastMean --
-RESIZE_INTERP = {'linear': 1, 'cubic': 2, 'area': 3, 'lanczos4': 4, 1: 1, 2: 2, 3: 3, 4: 4}
-FAST_FILTER_FN = {'median': 0, 'nanmedian': 1, 'mean': 2, 'nanmean': 3}
+RESIZE_INTERP = {'linear': L.RESIZE_LINEAR, 'cubic': L.RESIZE_CUBIC, 'area': L.RESIZE_AREA,
+                 'lanczos4': L.RESIZE_LANCZOS4}
+RESIZE_INTERP.update({v: v for v in list(RESIZE_INTERP.values())})   # cv2's INTER_* numbers as they are
+FAST_FILTER_FN = {'median': L.STAT_MEDIAN, 'nanmedian': L.STAT_NANMEDIAN, 'mean': L.STAT_MEAN,
+                  'nanmean': L.STAT_NANMEAN}
 
 
 def resize(img, dsize_hw, interpolation='linear', out=None, ctx=None, src_shape=None):

@@ -40,6 +40,65 @@ def test_abi_exports_every_declared_symbol():
     assert b'unsupported' in lib.ipa_status_string(-2)
 
 
+def _header_text():
+    return re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+
+
+def _param_class(decl):
+    """a C parameter -> 'ptr' for any pointer, else its scalar type"""
+    if '*' in decl:
+        return 'ptr'
+    words = decl.replace('const', ' ').split()[:-1]   # the last word is the parameter's name
+    return ' '.join(words)
+
+
+def _ctype_class(t):
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return 'ptr'
+    return {C.c_int: 'int', C.c_long: 'long', C.c_double: 'double', C.c_float: 'float',
+            C.c_size_t: 'size_t'}[t]
+
+
+def test_abi_prototypes_match_the_header():
+    """every `int ipa_*(...)` / `const char* ipa_*(...)` declaration against the argtypes the binding sets: the
+    same number of parameters, in the same order, each of the same class (any pointer, int, long, double, float,
+    size_t) - a long bound as int or a dropped parameter loads without error and hands a kernel garbage"""
+    from imgprocessor_amd import _lib
+    assert C.sizeof(C.c_long) == 8 and C.c_size_t is not C.c_long   # the classes below are distinct types
+    decls = re.findall(r'\b(int|const char\s*\*)\s+(ipa_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', _header_text())
+    assert sorted(n for _, n, _ in decls) == _declared_symbols(), 'a declaration the pattern does not parse'
+    for ret, name, params in decls:
+        table = _lib._CHARP if '*' in ret else _lib.PROTOTYPES
+        assert name in table, '%s returns %s: bound in the wrong table' % (name, ret)
+        params = [p.strip() for p in params.split(',')]
+        want = [] if params == ['void'] else [_param_class(p) for p in params]
+        assert set(want) <= {'ptr', 'int', 'long', 'double', 'float', 'size_t'}, (name, want)
+        got = [_ctype_class(t) for t in table[name]]
+        assert got == want, '%s: header %s, binding %s' % (name, want, got)
+
+
+def test_abi_enums_match_the_header():
+    """every IPA_<NAME> enumerator of the header has the same value as _lib.<NAME>: status, dtype, INTER_*, BORDER_*,
+    the op ids of the *_path queries, CV_TABLE_*, RESIZE_*"""
+    from imgprocessor_amd import _lib
+    seen = {}
+    for body in re.findall(r'typedef\s+enum\s*\{(.*?)\}', _header_text(), flags=re.S):
+        value = -1
+        for item in body.split(','):
+            if not item.strip():
+                continue
+            m = re.match(r'^\s*IPA_([A-Z0-9_]+)\s*(?:=\s*(\S+))?\s*$', item)
+            assert m, 'enumerator not understood: %r' % item
+            value = int(m.group(2), 0) if m.group(2) else value + 1   # without `= value`: one more
+            seen[m.group(1)] = value
+    assert len(seen) >= 57 and seen['ERR_NO_DEVICE'] == -5 and seen['INTER_Q5'] == 0x100
+    assert seen['STENCIL_CONV_YDEP'] == 8 and seen['RESIZE_LANCZOS4'] == 4
+    for name, value in seen.items():
+        assert hasattr(_lib, name), '_lib.py does not mirror IPA_%s' % name
+        assert getattr(_lib, name) == value, 'IPA_%s is %d in the header, %d in _lib.py' % (
+            name, value, getattr(_lib, name))
+
+
 def test_no_device_fails_loudly():
     """without a gfx950 device the context refuses to exist: no CPU fallback anywhere"""
     import imgprocessor_amd as ia
