@@ -141,6 +141,12 @@ PROTOTYPES = {
     'ipa_remove_single_pixels_dev': [_vp, _vp, _i, _i, _l, _vp, _l],
     'ipa_nl_means_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _i, _i, _d, _d, _vp, _l, _l],
     'ipa_nan_to_zero_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l],
+    'ipa_nlf_signal_dev': [_vp, _vp, _i, _vp, _i, _i, _l, _l, _vp, _l, _d, _vp, _l],
+    'ipa_nlf_moments_dev': [_vp, _vp, _i, _i, _i, _l, _dp],
+    'ipa_nlf_bins_dev': [_vp, _vp, _i, _vp, _i, _i, _l, _l, _vp, _l, _d, _vp, _l, _dp, _i, _d, _d,
+                         _i, _vp, _dp],
+    'ipa_snr_map_dev': [_vp, _vp, _i, _i, _l, _dp, _vp, _l, _d, _d, _d, _vp, _l],
+    'ipa_snr_bg_median_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

@@ -27,6 +27,12 @@ removal for image stacks (:388-408) and ``deblur`` (:439-444).  ``denoise`` (:45
 runs on the device (ops.nl_means).
 The reference always promotes the frame to float64 (:408-410); ``dtype=`` lets
 a caller keep float32 frames (half the HBM traffic) — an extension.
+
+A ``noise`` entry (``addNoise(nlf_coeff)``) is the (minY, ax, ay) triple of
+NoiseLevelFunction.boundedFunction.  To obtain one from frames:
+``NoiseLevelFunction.oneImageNLF(img)[0].triple`` (one frame, or two exposures
+of the same scene), or ``estimateFromImages(imgs1, imgs2)[5]`` over several
+pairs — the frame passes run on the device (csrc/nlf.hip).
 """
 from __future__ import print_function
 

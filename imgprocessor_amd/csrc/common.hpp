@@ -48,6 +48,7 @@ struct ipa_tuning {
   int chain_frames = 0;   // ... frames per workgroup (0: up to 8, by launch size)
 #endif
   int ste_frames = 8;     // frames per launch of the single-time-effect kernel (ste.hip): 8 on the halo tile, 1 one launch per frame
+  int nlf_grid = 0;       // workgroups of the persistent launches of nlf.hip (moments, bins): 0 by launch size, n exactly n
   int pipe7 = 1;          // 7x7 after a bilinear map remap of a batch: resident coefficients on the shared-map loop
   int frame_major = 1;    // kernels whose frames share nothing (plain filters): frame after frame, every
                           // XCD streaming through frames of its own

@@ -71,6 +71,7 @@ const TuneName kTuneNames[] = {
     {"frame_major", "IPA_FRAME_MAJOR", &ipa_tuning::frame_major},
     {"pipe7", "IPA_PIPE7", &ipa_tuning::pipe7},
     {"ste_frames", "IPA_STE_FRAMES", &ipa_tuning::ste_frames},
+    {"nlf_grid", "IPA_NLF_GRID", &ipa_tuning::nlf_grid},
     {"group_chunk", "IPA_GROUP_CHUNK", &ipa_tuning::group_chunk},
 #if IPA_WITH_TILE_CHAIN
     {"tile_chain", "IPA_TILE_CHAIN", &ipa_tuning::tile_chain},
@@ -100,6 +101,7 @@ static bool tune_in_range(const char* name, int v) {
   if (strcmp(name, "tail_rows") == 0) return v >= -1 && v <= 4096;
   if (strcmp(name, "tile_chain") == 0) return v >= 0 && v <= 2;
   if (strcmp(name, "ste_frames") == 0) return v == 1 || v == 8;
+  if (strcmp(name, "nlf_grid") == 0) return v >= 0 && v <= 4096;
   return v == 0 || v == 1;
 }
 

@@ -19,7 +19,7 @@
 // rounded: results equal numpy's bits.  FP contraction is off for this file (Makefile + pragma)
 // because numpy never fuses and a fused `x - a * sqrt(..)` would not round like it.
 #include "common.hpp"
-#include <float.h>
+#include "nlf_fn.hpp"
 
 #pragma clang fp contract(off)
 
@@ -34,20 +34,6 @@ constexpr int kSteH = kSteWaves * kSteRowsPerWave;   // tile height (output + ha
 constexpr int kSteMaxF = 8;                   // frames per launch of the halo kernel
 
 typedef unsigned long long u64;
-
-// numpy's maximum / minimum as they run here (np.max / np.min over axis 0, np.maximum): NaN in
-// either operand propagates; on equal operands the second one is returned.
-__device__ inline double np_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ inline double np_min(double a, double b) { return (a < b || a != a) ? a : b; }
-
-// boundedFunction(x, minY, ax, ay) = maximum(nan_to_num(ay * sqrt(x - ax)), minY)
-__device__ inline double bounded_nlf(double x, double min_y, double ax, double ay) {
-  double y = ay * sqrt(x - ax);
-  if (y != y) y = 0.0;
-  else if (y == __builtin_inf()) y = DBL_MAX;
-  else if (y == -__builtin_inf()) y = -DBL_MAX;
-  return np_max(y, min_y);
-}
 
 struct Row128 {
   u64 lo, hi;   // bit c of lo: column c, bit c of hi: column 64 + c

@@ -22,7 +22,8 @@ from ..device import DeviceArray, default_context
 
 def _nlf_triple(nlf):
     if callable(nlf):
-        return None
+        # an estimated NLF (NoiseLevelFunction.oneImageNLF) carries its parameters: device path
+        return getattr(nlf, 'triple', None)
     try:
         t = tuple(float(v) for v in nlf)
     except TypeError:
@@ -49,8 +50,9 @@ class SingleTimeEffectDetection(object):
       ``mask_STE``    True where any frame so far was an STE (None unless save_ste_indices)
       ``threshold``   nlf(min(images[0], images[1])) * nStd, fixed by the first pair
 
-    noise_level_function: a (minY, ax, ay) triple of NoiseLevelFunction.boundedFunction,
-    evaluated on the device, or any callable.  A callable is evaluated on the HOST on
+    noise_level_function: a (minY, ax, ay) triple of NoiseLevelFunction.boundedFunction or the
+    function NoiseLevelFunction.oneImageNLF returns (its ``.triple``), evaluated on the device,
+    or any callable.  Any other callable is evaluated on the HOST on
     min(images[0], images[1]) (float64, NaN propagating) and its threshold uploaded: a
     compatibility path with a device -> host -> device round trip for device frames.
     """

@@ -10,6 +10,9 @@ import numpy as np
 
 from . import _lib as L
 from .device import DeviceArray, default_context, dtype_id, as_frames
+from ._staging import _is_dev, _ctx_of, _p, _dptr, _dev_out, _stage_in, _stage_out  # noqa: F401
+# the noise-level-function / SNR family lives in ops_nlf.py
+from .ops_nlf import nlf_signal, nlf_moments, nlf_bins, snr_map, snr_bg_median  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)
@@ -48,33 +51,10 @@ def border_id(v):
     return int(v)
 
 
-def _is_dev(a):
-    return isinstance(a, DeviceArray)
-
-
-def _ctx_of(*arrs, **kw):
-    ctx = kw.get('ctx')
-    for a in arrs:
-        if _is_dev(a):
-            if ctx is not None and a.ctx is not ctx:
-                raise ValueError('arrays live on different contexts')
-            ctx = a.ctx
-    return ctx or default_context()
-
-
 def _host(a, dtype=None):
     a = np.ascontiguousarray(a, dtype=dtype)
     dtype_id(a.dtype)
     return a
-
-
-def _p(a):
-    return a.ptr if _is_dev(a) else a.ctypes.data_as(C.c_void_p)
-
-
-def _dptr(a):
-    """const double* to a C-contiguous float64 ndarray (the pointer keeps the array alive)"""
-    return a.ctypes.data_as(L._dp)
 
 
 def _mat3(M):
@@ -88,14 +68,6 @@ def _lens(K, dist5, newK):
 
 def _out_dtype(src_dtype, out_dtype):
     return np.dtype(src_dtype if out_dtype is None else out_dtype)
-
-
-def _dev_out(ctx, out, shape, dtype):
-    if out is None:
-        return DeviceArray(ctx, shape, dtype)
-    if not _is_dev(out) or out.shape != tuple(shape) or out.dtype != np.dtype(dtype):
-        raise ValueError('out must be a DeviceArray of shape %s dtype %s' % (shape, dtype))
-    return out
 
 
 # ------------------------------------------------------------------ maps --
@@ -396,31 +368,6 @@ def gaussian_filter(img, sigma, mode='reflect', cval=0.0, truncate=4.0, out=None
 
 
 _FLOATS = (np.float32, np.float64)
-
-
-def _stage_in(name, x, ctx, dtypes=None, host=None, others=(), ndims=(2,), bad_shape=ValueError):
-    """One image of a single-image op, host array or DeviceArray -> (dev, ctx, d_in, h, w).
-    A host array goes through `host` (which may refuse it; None: the op takes DeviceArrays
-    only) and up to the device.  `dtypes`: what the kernel takes (None: the library decides),
-    TypeError otherwise; `bad_shape`: what a wrong number of dimensions raises.  `others` may
-    be DeviceArrays too and must live on the same context."""
-    dev = _is_dev(x)
-    if not dev and host is None:
-        raise TypeError('%s needs a DeviceArray' % name)
-    ctx = _ctx_of(x, *others, ctx=ctx)
-    d_in = x if dev else ctx.to_device(host(x))
-    if dtypes is not None and d_in.dtype not in dtypes:
-        raise TypeError('%s needs %s arrays (got %s)'
-                        % (name, ' / '.join(np.dtype(t).name for t in dtypes), d_in.dtype))
-    if d_in.ndim not in ndims:
-        raise bad_shape('%s works on %s-D arrays (got shape %s)'
-                        % (name, ' / '.join(str(d) for d in ndims), d_in.shape))
-    return dev, ctx, d_in, d_in.shape[-2], d_in.shape[-1]
-
-
-def _stage_out(dev, d_out):
-    """the result as the input came: DeviceArray for a DeviceArray, numpy otherwise"""
-    return d_out if dev else d_out.get()
 
 
 def _nonzero_u8(a):

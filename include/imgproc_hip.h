@@ -101,6 +101,8 @@ int ipa_ctx_synchronize(ipa_ctx* ctx);
  *   the workgroups that run while the launch drains: -1 = the measured rule by taps and launch size, 0 = uniform
  *   strips, n = short strips of n rows; same bits).
  *   "ste_frames" (frames per launch of ipa_ste_dev: 8, the halo tile, default; 1, one launch per frame; same bits).
+ *   "nlf_grid" (workgroups of the persistent launches of ipa_nlf_moments_dev and ipa_nlf_bins_dev: 0, by launch size,
+ *   default; n <= 4096, exactly n whatever the work - idle workgroups contribute zeros).
  *   ipa_ctx_get_tuning also answers the read-only names "tail_rows_used" (height of the short strips of the last such
  *   launch, 0 = uniform), "rank1_routed" (dense calls sent to the separable loops so far) and "group_chunk_used" (frame
  *   groups per chunk of the last launch on the shared-record loop; "group_chunk" values that do not divide
@@ -655,6 +657,66 @@ int ipa_nl_means_dev(ipa_ctx* ctx, const void* d_src, int dtype, int n, int h, i
 /* image[isnan(image)] = 0 (camera/CameraCalibration.py:467), in place, IPA_F32 / IPA_F64 */
 int ipa_nan_to_zero_dev(ipa_ctx* ctx, void* d_img, int dtype, int n, int h, int w, long pitch,
                         long frame_stride);
+
+/* ---------------------------------------------------------------- noise level function, SNR */
+/* The frames of these calls are uint8 / uint16 / float32 / float64 (IPA_ERR_UNSUPPORTED otherwise),
+ * h x w with a pitch in elements, at most 2^30 pixels; all arithmetic is float64 (the reference
+ * starts with np.asfarray) and every operation is correctly rounded and unfused.  d_img2 (same
+ * dtype, pitch2) is the second exposure or NULL.  A frame is read as `img - bg` with bg the
+ * float64 array d_bg (bg_pitch) or, where that is NULL, the scalar `bg` (measure/SNR/SNR.py:33-40;
+ * calcNLF passes NULL and 0.0: x - 0.0 is x). */
+
+/* replaces camera/NoiseLevelFunction.py:208-228 and measure/SNR/SNR.py:37-47 (the signal):
+ *   one image:   signal = scipy.ndimage.median_filter(img, 3)
+ *   two images:  signal = median_filter(0.5 * (img + img2), 3)
+ * rank 4 of the 9 values, the edge pixel repeated; written as float64.  Bit-equal to scipy for
+ * frames without NaN; a NaN in the window gives NaN (scipy's answer there is unspecified).  Not in
+ * place. */
+int ipa_nlf_signal_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_img2, int h, int w,
+                       long pitch, long pitch2, const double* d_bg, long bg_pitch, double bg,
+                       double* d_signal, long signal_pitch);
+/* replaces camera/NoiseLevelFunction.py:162-173 (_getMinMax: img.min(), img.max(), np.mean, np.std):
+ * moments[0 ... 4] (HOST) = min, max, mean, population std of the non-NaN values of the frame d_img
+ * (any of the four types, read as float64: the signal, or a raw frame as estimateFromImages passes
+ * one), and the number of NaN values.  Two passes (sum; sum of (x - mean)^2) through per-workgroup
+ * partials added in workgroup order: no float atomics, the same bits for the same grid.  Uses the
+ * context workspace; returns after the stream has drained. */
+int ipa_nlf_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                        double* moments);
+/* replaces the loop of camera/NoiseLevelFunction.py:243-271 (and the constant noise level of
+ * measure/SNR/SNR.py:50-58 with one bin):
+ *   diff = (img - signal) * factor        one image  (factor 1 + 1/9, or 1 with
+ *                                                     signalFromMultipleImages)
+ *   diff = (img - img2) / factor          two images (factor 2**0.5; a division, as in :226)
+ *   bin n = every pixel with edges[n] <= signal <= edges[n + 1], BOTH ends inclusive (:259): a
+ *           pixel on an interior edge counts in two bins, a NaN signal in none
+ *   counts[n] = pixels of bin n (exact), sums[n] = sum |diff| (rms 0) or sum diff^2 (rms 1)
+ * edges (nbins + 1 doubles, HOST) is the reference's table e[0] = mn, e[k + 1] = e[k] + step and
+ * `step` its step: the kernel guesses floor((signal - e[0]) / step) and settles membership of that
+ * bin and its two neighbours against the table.  step > 0 (or 0 with nbins 1: every pixel equal
+ * to the one edge).  counts and sums are HOST arrays of nbins.  1 <= nbins <= 2048; above that
+ * IPA_ERR_UNSUPPORTED and nothing is written.  Per-workgroup slabs added in workgroup order: no
+ * float atomics on global memory.  Uses the context workspace; returns after the stream has
+ * drained. */
+int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_img2, int h, int w,
+                     long pitch, long pitch2, const double* d_bg, long bg_pitch, double bg,
+                     const double* d_signal, long signal_pitch, const double* edges, int nbins,
+                     double step, double factor, int rms, unsigned long long* counts, double* sums);
+/* replaces measure/SNR/SNR.py:59-79 per pixel of the float64 signal:
+ *   noise = max(nan_to_num(ay * sqrt(signal - ax)), minY), then 1 where below 1   nlf = {minY, ax, ay} (HOST)
+ *         = d_noise[y, x], then 1 where below 1     nlf NULL: a noise level function evaluated by the caller
+ *         = const_noise                             both NULL: constant_noise_level (:50-58, not clamped)
+ *   noise = noise * noise_factor                    0.5**0.5 for imgs_to_be_averaged, else 1
+ *   snr   = (signal - bg_level) / noise, then 1 where below 1; NaN stays NaN
+ * bg_level: the estimated background (:72-74), 0 where the caller's bg was subtracted already. */
+int ipa_snr_map_dev(ipa_ctx* ctx, const double* d_signal, int h, int w, long pitch, const double* nlf,
+                    const double* d_noise, long noise_pitch, double const_noise, double noise_factor,
+                    double bg_level, double* d_snr, long snr_pitch);
+/* replaces the filter of measure/SNR/SNR.py:82-87 (getBackgroundLevel): d_grid (float64,
+ * ceil((h - 20) / 10) x ceil((w - 20) / 10)) = median_filter(img[10:-10:10, 10:-10:10], 3); h, w > 20.
+ * The caller takes the 1 % point of its histogram (utils/cdf.py:7-20). */
+int ipa_snr_bg_median_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                          double* d_grid, long grid_pitch);
 
 #ifdef __cplusplus
 }
