@@ -38,6 +38,9 @@ CONV_CONV2D, CONV_SEPCONV2D, CONV_SEPCONV2D_LDS = range(3)
 RESIZE_LINEAR, RESIZE_CUBIC, RESIZE_AREA, RESIZE_LANCZOS4 = 1, 2, 3, 4
 STAT_MEDIAN, STAT_NANMEDIAN, STAT_MEAN, STAT_NANMEAN = range(4)
 
+# ipa_nlf_kind of ipa_nlf_threshold_dev
+NLF_BOUNDED_SQRT, NLF_CLIPPED_POLY, NLF_CONSTANT = range(3)
+
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t
@@ -147,6 +150,11 @@ PROTOTYPES = {
                          _i, _vp, _dp],
     'ipa_snr_map_dev': [_vp, _vp, _i, _i, _l, _dp, _vp, _l, _d, _d, _d, _vp, _l],
     'ipa_snr_bg_median_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l],
+    'ipa_pair_min_dev': [_vp, _vp, _vp, _i, _i, _i, _l, _l, _vp, _l],
+    'ipa_nlf_threshold_dev': [_vp, _vp, _i, _i, _l, _i, _dp, _d, _vp, _l],
+    'ipa_stack_linregress_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _dp, _d, _d, _vp, _vp, _vp, _l],
+    'ipa_dark_current_eval_dev': [_vp, _vp, _vp, _i, _i, _l, _d, _d, _vp, _i, _l],
+    'ipa_cast_trunc_dev': [_vp, _vp, _i, _i, _l, _vp, _i, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

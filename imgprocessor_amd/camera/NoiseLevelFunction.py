@@ -20,7 +20,10 @@ Differences from the reference, all at its undefined corners:
     min / max is ill-defined there); with ``mn_mx_nbins`` a NaN pixel counts in no bin.
   - the function ``oneImageNLF`` / ``_evaluate`` return is an object with a ``.triple =
     (minY, ax, ay)`` attribute - SingleTimeEffectDetection and SNR evaluate it on the device -
-    unless the polynomial fallback was taken.
+    unless the polynomial fallback was taken: then it is a ``ClippedPolyNLF`` with ``.poly =
+    (p2, p1, p0, x0, x1)`` or a ``ConstantNLF`` with ``.constant``, which SingleTimeEffectDetection
+    evaluates on the device too (the reference returns bare lambdas; the call results are the same
+    bits).
   - ``estimateFromImages`` takes arrays, not file paths.
 """
 import numpy as np
@@ -42,6 +45,31 @@ class BoundedNLF(object):
 
     def __call__(self, x):
         return boundedFunction(x, *self.triple)
+
+
+class ClippedPolyNLF(object):
+    """smooth()'s second-order polynomial, held to the range it was fitted on: fn(x) on the host,
+    fn.poly = (p2, p1, p0, x0, x1) for the device (ops.nlf_threshold).  No ``.triple``: it is no
+    square root."""
+
+    def __init__(self, p, x0, x1):
+        self._p = np.array(p, dtype=np.float64)
+        self.poly = tuple(float(v) for v in self._p) + (float(x0), float(x1))
+
+    def __call__(self, xint):
+        return np.poly1d(self._p)(np.clip(xint, self.poly[3], self.poly[4]))
+
+
+class ConstantNLF(object):
+    """smooth()'s last resort, one noise level for every intensity: fn(x) on the host,
+    fn.constant for the device"""
+
+    def __init__(self, my):
+        self._my = my
+        self.constant = float(my)
+
+    def __call__(self, x):
+        return self._my
 
 
 def estimateFromImages(imgs1, imgs2=None, mn_mx=None, nbins=100):
@@ -131,9 +159,8 @@ def smooth(x, y, weights):
     constant where even that cannot be fitted"""
     p = np.polyfit(x, y, w=weights, deg=2)
     if np.any(np.isnan(p)):
-        my = np.average(y, weights=weights)
-        return lambda x: my
-    return lambda xint: np.poly1d(p)(np.clip(xint, x[0], x[-1]))
+        return ConstantNLF(np.average(y, weights=weights))
+    return ClippedPolyNLF(p, x[0], x[-1])
 
 
 def oneImageNLF(img, img2=None, signal=None):

@@ -51,8 +51,9 @@ class SingleTimeEffectDetection(object):
       ``threshold``   nlf(min(images[0], images[1])) * nStd, fixed by the first pair
 
     noise_level_function: a (minY, ax, ay) triple of NoiseLevelFunction.boundedFunction or the
-    function NoiseLevelFunction.oneImageNLF returns (its ``.triple``), evaluated on the device,
-    or any callable.  Any other callable is evaluated on the HOST on
+    function NoiseLevelFunction.oneImageNLF returns (its ``.triple``, or the ``.poly`` /
+    ``.constant`` of its polynomial fallback), evaluated on the device, or any callable.  Any
+    other callable is evaluated on the HOST on
     min(images[0], images[1]) (float64, NaN propagating) and its threshold uploaded: a
     compatibility path with a device -> host -> device round trip for device frames.
     """
@@ -109,7 +110,15 @@ class SingleTimeEffectDetection(object):
             self._ste = DeviceArray(ctx, (h, w), np.uint8)
             ctx._check(ctx._lib.ipa_memset(ctx.handle, self._ste.ptr, 0, self._ste.nbytes),
                        'memset')
-        if triple is None:
+        if triple is None and ops.nlf_params(noise_level_function) is not None:
+            # the polynomial or the constant NoiseLevelFunction.smooth falls back to (what dark
+            # frames take): min(f0, f1) and the threshold on the device, nothing comes down
+            if not self._dev:
+                f = np.asarray(frames)
+                frames = ctx.to_device(f if f.dtype in ops.STE_DTYPES else f.astype(np.float64))
+            m = ops.pair_min(frames.frame(0), frames.frame(1))
+            ops.nlf_threshold(m, noise_level_function, nStd, out=self._thr)
+        elif triple is None:
             # host-evaluated NLF: threshold of min(f0, f1) in float64, as the reference (:39-44)
             if self._dev:
                 f01 = np.stack([frames.frame(0).get(), frames.frame(1).get()])

@@ -13,6 +13,9 @@ from .device import DeviceArray, default_context, dtype_id, as_frames
 from ._staging import _is_dev, _ctx_of, _p, _dptr, _dev_out, _stage_in, _stage_out  # noqa: F401
 # the noise-level-function / SNR family lives in ops_nlf.py
 from .ops_nlf import nlf_signal, nlf_moments, nlf_bins, snr_map, snr_bg_median  # noqa: F401
+# the dark-current family lives in ops_dark.py
+from .ops_dark import (pair_min, nlf_threshold, stack_linregress, dark_current_eval,  # noqa: F401
+                       cast_trunc, nlf_params)
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -718,6 +718,69 @@ int ipa_snr_map_dev(ipa_ctx* ctx, const double* d_signal, int h, int w, long pit
 int ipa_snr_bg_median_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
                           double* d_grid, long grid_pitch);
 
+/* ---------------------------------------------------------------- dark current calibration */
+/* What camera/DarkCurrentMap.py needs around ipa_ste_dev.  Frames are uint8 / uint16 / float32 /
+ * float64 (IPA_ERR_UNSUPPORTED otherwise), pitches in elements; all arithmetic is float64, every
+ * operation correctly rounded and unfused, NaN propagates as numpy propagates it. */
+
+/* replaces np.min((i1, i2), axis=0) of features/SingleTimeEffectDetection.py:39-42, the image the
+ * reference hands to oneImageNLF: d_out (float64) = min(f0, f1), a NaN in either frame wins.  Both
+ * frames have the type `dtype`.  Not in place. */
+int ipa_pair_min_dev(ipa_ctx* ctx, const void* d_f0, const void* d_f1, int dtype, int h, int w, long pitch0,
+                     long pitch1, double* d_out, long out_pitch);
+
+typedef enum {
+  IPA_NLF_BOUNDED_SQRT = 0, /* {minY, ax, ay}:        max(nan_to_num(ay * sqrt(x - ax)), minY)        */
+  IPA_NLF_CLIPPED_POLY = 1, /* {p2, p1, p0, x0, x1}:  np.poly1d(p)(np.clip(x, x0, x1))                */
+  IPA_NLF_CONSTANT = 2      /* {c}:                   c, whatever x is                                */
+} ipa_nlf_kind;
+/* replaces `noise_level_function(self.mma.avg) * nStd` of features/SingleTimeEffectDetection.py:44
+ * for the three functions camera/NoiseLevelFunction.py:94-151 (_evaluate, smooth) can return:
+ * d_thr = nlf(d_x) * nstd over a float64 frame.  The bounded square root is the arithmetic of the
+ * first pair of ipa_ste_dev.  The polynomial runs in numpy's Horner order ((0*c + p2)*c + p1)*c + p0
+ * on c = minimum(maximum(x, x0), x1); a NaN x gives NaN.  params is a HOST pointer to 3 / 5 / 1
+ * doubles; an unknown kind is IPA_ERR_BAD_ARG.  d_thr may be d_x itself (same pitch). */
+int ipa_nlf_threshold_dev(ipa_ctx* ctx, const double* d_x, int h, int w, long pitch, int kind,
+                          const double* params, double nstd, double* d_thr, long thr_pitch);
+
+/* replaces getLinearityFunction of camera/DarkCurrentMap.py:61-80 in one launch: per pixel of a
+ * (T, h, w) stack the line image(t) = offset + ascent * t through the samples that are not above
+ * mx_intensity.  times: T doubles (HOST).  Sample k is valid where !(y[k] > mx_intensity) - the
+ * reference masks `imgs > mxIntensity`, so a NaN sample is valid and poisons its pixel.  In frame
+ * order, masked samples adding nothing:
+ *   n  = #valid;  mx = sum(x[k]) / n;  my = sum(y[k]) / n
+ *   sxx = sum((x[k]-mx)*(x[k]-mx));  sxy = sum((x[k]-mx)*(y[k]-my))
+ *   ascent = sxy / sxx;  offset = my - ascent*mx
+ *   error  = sqrt(sum((y[k] - (offset + ascent*x[k]))^2) / n)          the fit's rms residual
+ * then the reference's own steps (:73-78):
+ *   ascent = 0 where NaN
+ *   min_ascent > 0: where ascent < min_ascent: offset += 0.5*(min(x)+max(x)) * ascent, ascent = 0
+ * min(x), max(x) over all T times (np.min(expTimes)).  A pixel with n <= 1 ends with ascent 0 and
+ * NaN in offset and error.
+ * UNPINNED: fancytools.math.linRegressUsingMasked2dArrays, which the reference calls for the first
+ * block, is neither in the reference tree nor installed where the fixtures are generated; the
+ * least-squares definition above is this project's (as the running mean of ipa_ste_dev is).
+ * 2 <= T <= 64 (above: IPA_ERR_UNSUPPORTED, nothing written; below: IPA_ERR_BAD_ARG).  d_offset,
+ * d_ascent, d_error: float64, out_pitch; stack and outputs must not overlap (IPA_ERR_BAD_ARG).
+ * For T <= 16 a pixel's samples stay in registers between the sums: every frame value is read
+ * once.  Longer stacks read them once per sum. */
+int ipa_stack_linregress_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int T, int h, int w, long pitch,
+                             long frame_stride, const double* times, double mx_intensity, double min_ascent,
+                             double* d_offset, double* d_ascent, double* d_error, long out_pitch);
+
+/* the model camera/CameraCalibration.py:509-519 (calcDarkCurrent) holds: bg = offset + ascent * t,
+ * then `limit` where that exceeds it; NaN is kept.  d_out is IPA_F32 or IPA_F64 (IPA_ERR_UNSUPPORTED
+ * otherwise), rounded once from the float64 value.  Not in place. */
+int ipa_dark_current_eval_dev(ipa_ctx* ctx, const double* d_offset, const double* d_ascent, int h, int w,
+                              long pitch, double t, double limit, void* d_out, int out_dtype, long out_pitch);
+
+/* replaces `i[:] = avg` of camera/DarkCurrentMap.py:108-114 (the averages stack has the type of
+ * imgs[0]): float64 -> uint8 / uint16 / float32 / float64 by C conversion, integers truncated
+ * toward zero.  Defined for finite values inside the target's range; NaN into a float type stays
+ * NaN.  Not in place. */
+int ipa_cast_trunc_dev(ipa_ctx* ctx, const double* d_in, int h, int w, long pitch, void* d_out, int out_dtype,
+                       long out_pitch);
+
 #ifdef __cplusplus
 }
 #endif
