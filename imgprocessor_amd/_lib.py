@@ -41,6 +41,11 @@ STAT_MEDIAN, STAT_NANMEDIAN, STAT_MEAN, STAT_NANMEAN = range(4)
 # ipa_nlf_kind of ipa_nlf_threshold_dev
 NLF_BOUNDED_SQRT, NLF_CLIPPED_POLY, NLF_CONSTANT = range(3)
 
+# IPA_REMAP_PATH_* bits of the read-only tuning word "remap_path"
+(REMAP_PATH_GATHER, REMAP_PATH_REST, REMAP_PATH_RING, REMAP_PATH_TILE, REMAP_PATH_TILE_MAP,
+ REMAP_PATH_STORED, REMAP_PATH_U8_LZ_LDS, REMAP_PATH_STRIP, REMAP_PATH_STRIP_INT, REMAP_PATH_LENS_MAP,
+ REMAP_PATH_FRAMES_INNER) = (1 << k for k in range(11))
+
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 
 _vp, _i, _l, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_double, C.c_size_t

@@ -328,6 +328,7 @@ int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int 
   if (rc) return rc;
   IPA_HIP(ctx, hipGetLastError());
   ctx->strip_remaps++;
+  ctx->remap_path |= IPA_REMAP_PATH_STRIP_INT;
   return IPA_OK;
 }
 

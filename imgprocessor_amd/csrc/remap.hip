@@ -186,6 +186,7 @@ int ipa_remap_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, int sw
                   long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
                   double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->remap_path = 0;
   IPA_REQUIRE(ctx, d_mapx && d_mapy && map_pitch >= dw, "bad map arguments");
   if ((src_dtype == IPA_U16 || src_dtype == IPA_U8) && dst_dtype == src_dtype) {
     // ... and INTO the frames' own integer type with cv2's arithmetic (what LensDistortion.correct returns for camera
@@ -198,10 +199,12 @@ int ipa_remap_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, int sw
   }
   if (strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp, 0, false)) {
     ctx->strip_remaps++;
-    return ipa_remap_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, &kOneTap, 1,
+    const int crc = ipa_remap_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, d_mapx, d_mapy, map_pitch, &kOneTap, 1,
                                    &kOneTap, 1, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                                    dst_frame_stride, interp, border_mode, border_value, IPA_BORDER_REFLECT,
                                    IPA_BORDER_REFLECT);
+    if (crc == IPA_OK) ctx->remap_path |= IPA_REMAP_PATH_STRIP;   // (the chain's own checks passed: enqueued)
+    return crc;
   }
   MapCoord c{d_mapx, d_mapy, map_pitch};
   int map_vec = aligned_rows(d_mapx, map_pitch, 0, 1, 4, IPA_VEC_ALIGN) &&
@@ -217,16 +220,19 @@ int ipa_undistort_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, in
                       long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
                       double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->remap_path = 0;
   UndistortCoord c;
   int rc = make_undistort_coord(ctx, K, dist5, newK, &c);
   if (rc) return rc;
   if (ctx->tune.lens_cache && src_dtype == IPA_U16 &&   // (through the cached map; uint8 frames: ipa_remap_dev below)
       strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp, 0, true)) {
     ctx->strip_remaps++;
-    return ipa_undistort_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, &kOneTap, 1, &kOneTap,
+    const int crc = ipa_undistort_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, K, dist5, newK, &kOneTap, 1, &kOneTap,
                                        1, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                                        dst_frame_stride, interp, border_mode, border_value, IPA_BORDER_REFLECT,
                                        IPA_BORDER_REFLECT);
+    if (crc == IPA_OK) ctx->remap_path |= IPA_REMAP_PATH_STRIP;   // (the chain's own checks passed: enqueued)
+    return crc;
   }
   // integer frames, batches: the model's float32 coordinates are the same for every frame - through the cached
   // map (bit for bit what the per-pixel evaluation gives; the chains have used it since round 2) instead of
@@ -235,8 +241,10 @@ int ipa_undistort_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, in
     float *mx = nullptr, *my = nullptr;
     rc = ipa_lens_map_cached(ctx, K, dist5, newK, dh, dw, &mx, &my);
     if (rc) return rc;
-    return ipa_remap_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, mx, my, dw, d_dst, dst_dtype, dh, dw, dst_pitch,
-                         n_frames, src_frame_stride, dst_frame_stride, interp, border_mode, border_value);
+    rc = ipa_remap_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, mx, my, dw, d_dst, dst_dtype, dh, dw, dst_pitch,
+                       n_frames, src_frame_stride, dst_frame_stride, interp, border_mode, border_value);
+    ctx->remap_path |= IPA_REMAP_PATH_LENS_MAP;   // (ipa_remap_dev cleared the word on its entry: one word for the whole call)
+    return rc;
   }
   RemapCall a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch,
               n_frames, src_frame_stride, dst_frame_stride, interp, border_mode, border_value};
@@ -249,15 +257,18 @@ int ipa_warp_perspective_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
                              long dst_frame_stride, int interp, int border_mode,
                              double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->remap_path = 0;
   IPA_REQUIRE(ctx, M, "null matrix");
   if (strip_remap_takes(ctx, d_src, d_dst, src_dtype, dst_dtype, sh, sw, src_pitch, dh, dw, dst_pitch, n_frames, interp,
                         2, false) &&
       homography_row_drift(M, dh, dw) < 0.2) {   // (see ipa_remap_dev; pictures that turn stay with the gather kernels)
     ctx->strip_remaps++;
-    return ipa_warp_perspective_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, &kOneTap, 1, &kOneTap, 1,
+    const int crc = ipa_warp_perspective_sepconv2d_dev(ctx, d_src, src_dtype, sh, sw, src_pitch, M, &kOneTap, 1, &kOneTap, 1,
                                               d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                                               dst_frame_stride, interp, border_mode, border_value,
                                               IPA_BORDER_REFLECT, IPA_BORDER_REFLECT);
+    if (crc == IPA_OK) ctx->remap_path |= IPA_REMAP_PATH_STRIP;   // (the chain's own checks passed: enqueued)
+    return crc;
   }
   HomographyCoord c;
   for (int i = 0; i < 9; i++) c.m[i] = M[i];
@@ -274,6 +285,7 @@ int ipa_warp_grid_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh, in
                       long src_frame_stride, long dst_frame_stride, int interp, int border_mode,
                       double border_value) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->remap_path = 0;
   RemapCall a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch,
               n_frames, src_frame_stride, dst_frame_stride, interp, border_mode, border_value};
   return ipa_remap_launch_grid(ctx, a, cell_rects, cell_M, n_cells);

@@ -441,6 +441,7 @@ static void ring_remap_launch_one(ipa_ctx* ctx, const RingGeom& gm, const RingRe
   const unsigned groups = ((unsigned)ra.n_frames + RK::kWaves - 1) / RK::kWaves;
   hipLaunchKernelGGL((ring_remap_kernel<INTERP, Coord>), dim3((unsigned)gm.strips * groups),
                      dim3(64 * RK::kWaves), 0, ctx->stream, gm, ra, coord, plan);
+  ctx->remap_path |= IPA_REMAP_PATH_RING;
 }
 
 template <typename Coord>
@@ -590,6 +591,7 @@ static int tile_warp_launch(ipa_ctx* ctx, const RemapParams& p, const Homography
   const size_t lds = (size_t)tile_warp_lds_bytes<NT>(t.pitch, t.rows);
   if (shape == 0) tile_warp_run_a(ctx->stream, t, coord, INTERP, kU16, shape, (unsigned)t.tiles * groups, lds);
   else tile_warp_run_b(ctx->stream, t, coord, INTERP, kU16, shape, (unsigned)t.tiles * groups, lds);
+  ctx->remap_path |= IPA_REMAP_PATH_TILE;
   return 0;
 }
 
@@ -697,6 +699,7 @@ static int tile_warp_launch_map(ipa_ctx* ctx, const RemapParams& p, const MapCoo
   }
   tile_warp_run_map(ctx->stream, t, coord, INTERP, (unsigned)t.tiles * groups,
                     (size_t)tile_warp_lds_bytes<NT>(t.pitch, t.rows));
+  ctx->remap_path |= IPA_REMAP_PATH_TILE_MAP;
   IPA_HIP(ctx, hipMemcpyAsync(ctx->tile_slow_host + hslot, ctx->tile_slow_dev + hslot, sizeof(unsigned),
                               hipMemcpyDeviceToHost, ctx->stream));
   IPA_HIP(ctx, hipEventRecord(hint->copied, ctx->stream));
@@ -865,6 +868,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
       const unsigned bands = ((unsigned)a.dh + 16u * p.tile_rows - 1u) / (16u * p.tile_rows);
       hipLaunchKernelGGL((remap_u8_lz_kernel<Coord>), dim3(p.tiles_x * bands * (unsigned)a.n_frames),
                          dim3(1024), 0, ctx->stream, p, coord);
+      ctx->remap_path |= IPA_REMAP_PATH_U8_LZ_LDS;
       IPA_HIP(ctx, hipGetLastError());
       return IPA_OK;
     }
@@ -880,6 +884,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
         RemapParams q = p;
         q.map_vec = 1;   // rows of dw coordinates, 256-byte aligned planes
         launch_interp<float, float, StoredCoord<typename Coord::coord_t>, false>(ctx, q, sc, base, grid);
+        ctx->remap_path |= IPA_REMAP_PATH_STORED;
         IPA_HIP(ctx, hipGetLastError());
         return IPA_OK;
       }
@@ -914,6 +919,7 @@ static int remap_dispatch(ipa_ctx* ctx, const RemapCall& a, const Coord& coord, 
   } else {
     IPA_UNSUPPORTED(ctx, "remap: src dtype %d -> dst dtype %d not supported", s, d);
   }
+  ctx->remap_path |= (rest ? IPA_REMAP_PATH_REST : IPA_REMAP_PATH_GATHER) | (inner ? IPA_REMAP_PATH_FRAMES_INNER : 0);
   IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
 }

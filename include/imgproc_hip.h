@@ -95,6 +95,11 @@ int ipa_ctx_synchronize(ipa_ctx* ctx);
  *   arithmetic (IPA_INTER_LINEAR | IPA_INTER_Q5), uint8 into uint8 with its 8U fixed point; ipa_remap_dev, ipa_undistort_dev,
  *   ipa_warp_perspective_dev - on the marching strips of the chains with no filter: default 1; read-only counter
  *   "strip_remaps").
+ *   Read-only "remap_path": the kernels the last ipa_remap_dev / ipa_undistort_dev / ipa_warp_perspective_dev /
+ *   ipa_warp_grid_dev call enqueued, as IPA_REMAP_PATH_* bits (below).  The outermost of these calls clears the word on
+ *   entry - ipa_undistort_dev's pass through its cached map into ipa_remap_dev keeps one word for the whole call; after
+ *   a remap -> filter chain of two launches it describes that chain's remap -, every launch site sets its bit where the
+ *   kernel is enqueued.  Written on the host, once per launch; no routing decision reads it.
  *   "sep_u16" (uint16 frames, bilinear remap by maps or a homography -> separable 3 / 5 / 7 / 9-tap filter in one kernel: default 1;
  *   0 = two launches through the workspace).
  *   "tail_rows" (chunked batches on the shared-record loop end every XCD's share of the launch on short strips -
@@ -110,6 +115,19 @@ int ipa_ctx_synchronize(ipa_ctx* ctx);
  * Values are range-checked (IPA_ERR_BAD_ARG).  ipa_ctx_create reads the IPA_* environment
  * defaults once; no launch path consults the environment.  The reference has no counterpart
  * (its numba / cv2 calls take no launch parameters). */
+enum {                                    /* bits of the read-only "remap_path" (csrc/remap_impl.hpp, remap.hip, fused.hip) */
+  IPA_REMAP_PATH_GATHER = 1 << 0,       /* remap_kernel on the caller's coordinates (the uint8 bicubic table form too) */
+  IPA_REMAP_PATH_REST = 1 << 1,         /* remap_kernel behind a ring kernel's skip mask */
+  IPA_REMAP_PATH_RING = 1 << 2,         /* ring_remap_kernel */
+  IPA_REMAP_PATH_TILE = 1 << 3,         /* the tile kernel of a homography, float32 or uint16 */
+  IPA_REMAP_PATH_TILE_MAP = 1 << 4,     /* the tile kernel of a map pair */
+  IPA_REMAP_PATH_STORED = 1 << 5,       /* remap_kernel on coordinates evaluated once into the plan buffer */
+  IPA_REMAP_PATH_U8_LZ_LDS = 1 << 6,    /* remap_u8_lz_kernel */
+  IPA_REMAP_PATH_STRIP = 1 << 7,        /* the marching strips of the chains, into float32 */
+  IPA_REMAP_PATH_STRIP_INT = 1 << 8,    /* ... into the frames' own integer type */
+  IPA_REMAP_PATH_LENS_MAP = 1 << 9,     /* ipa_undistort_dev through its cached map */
+  IPA_REMAP_PATH_FRAMES_INNER = 1 << 10 /* the gather / rest launch had the frame index fastest */
+};
 int ipa_ctx_set_tuning(ipa_ctx* ctx, const char* name, int value);
 int ipa_ctx_get_tuning(ipa_ctx* ctx, const char* name, int* value);
 /* name (e.g. "gfx950...") and compute-unit count of the context's device */

@@ -76,7 +76,9 @@ def fit_pair():
 SHAPES = [(1, 1), (3, 67), (33, 130)]
 # the fit also where a row spans several tiles of lanes that own 4 (uint8, uint16) or 2 (float32) pixels
 REGRESS_SHAPES = SHAPES + [(5, 520)]
-T_VALUES = [2, 3, 16, 17, 64]
+# (both sides of every step of the fit's register count, stack_linregress_kernel<T, 4 | 8 | 16 | ...>:
+# 4 | 5 and 8 | 9 as well as 16 | 17 - stacks of 5 to 8 frames are an instantiation of their own)
+T_VALUES = [2, 3, 4, 5, 8, 9, 16, 17, 64]
 ALL_DTYPES = (np.uint8, np.uint16, np.float32, np.float64)
 
 

@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from .gpu_helpers import frames, kern, radial_maps, same_bits
+from .gpu_helpers import (frames, fresh_ring_hint, kern, only_gather, path_names, radial_maps, remap_path,
+                          same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,10 @@ def test_remap_with_pitches(ia, interp, tune, odd):
     try:
         ref_knobs = ctx.set_tuning(tile_warp=0, ring_remap=0)   # the reference: the plain gather kernel
         want = ops.remap(ctx.to_device(src), ctx.to_device(mx), ctx.to_device(my), interp).get()
+        ref_path = remap_path(ctx)
         ctx.set_tuning(**{k: v for k, v in ref_knobs.items()})
+        if tune.get('ring_remap'):
+            fresh_ring_hint(ctx)     # (no hint of an earlier call with these pointers decides)
         # pitches (elements): rows 16-byte aligned, or (odd) at every 4-byte alignment
         sp, dp, mp = w + 24 + odd, w + 8 + 3 * odd, w + 12 + odd
         sbig = ctx.to_device(_embed(src, sp - w, 5, 7.0))
@@ -52,9 +56,17 @@ def test_remap_with_pitches(ia, interp, tune, odd):
             ctx.handle, sbig.ptr, dtype_id(np.float32), h, w, sp, mbx.ptr, mby.ptr, mp, dbig.ptr,
             dtype_id(np.float32), h, w, dp, n, (h + 5) * sp, (h + 3) * dp, ops.interp_id(interp),
             ops.border_id('constant'), 0.0), 'remap')
+        path = remap_path(ctx)
         got = dbig.get()
     finally:
         ctx.set_tuning(**old)
+    # the kernels the parametrisation is named for ran, and the reference was the gather kernel alone
+    from imgprocessor_amd import _lib
+    assert only_gather(ref_path), 'the reference launched ' + path_names(ref_path)
+    alt = path & ~(_lib.REMAP_PATH_GATHER | _lib.REMAP_PATH_FRAMES_INNER)
+    want_alt = (_lib.REMAP_PATH_RING | _lib.REMAP_PATH_REST if tune.get('ring_remap') else
+                _lib.REMAP_PATH_TILE_MAP if tune.get('tile_warp') else 0)
+    assert alt == want_alt, '%r launched %s' % (tune, path_names(path))
     same_bits(np.ascontiguousarray(got[:, :h, :w]), want, 'pitched remap ' + interp)
     assert (got[:, h:, :] == -5.0).all() and (got[:, :, w:] == -5.0).all(), 'wrote outside'
 

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 from .conftest import assert_close
-from .gpu_helpers import frames, radial_maps, rot_maps, same_bits
+from .gpu_helpers import (frames, fresh_ring_hint, only_gather, path_names, radial_maps, remap_path, rot_maps,
+                          same_bits)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +28,33 @@ def orc_interp(oracle, name):
             'cubic_cv_q5': oracle.CUBIC_CV | oracle.Q5, 'lanczos4': oracle.LANCZOS4}[name]
 
 
-def both(ia, fn):
-    """fn() with the gather kernel alone, then with the ring kernel taking the clean strips"""
+def both(ia, fn, ring=True):
+    """fn() with the gather kernel alone, then with the ring kernel taking the clean strips - and the
+    evidence that this is what ran (read-only "remap_path"): the first call launched the gather kernel
+    and nothing else, the second the ring kernel and the gather launch behind its skip mask.  The tile
+    kernel and the stored coordinates are off for both (they would take some of these calls before the
+    ring is asked), and a ring call with a key of its own goes before the second run: the one-slot hint
+    of ring_plan_prepare otherwise sends a repeated key with few clean strips (rot90, shift_out under a
+    second border mode) to the gather kernel, which then is compared with itself.
+    ring=False: a call the ring kernel does not cover must not have launched it."""
+    from imgprocessor_amd import _lib
     ctx = ia.default_context(0)
-    old = ctx.set_tuning(ring_remap=0, ring_min=1)
+    old = ctx.set_tuning(ring_remap=0, ring_min=1, tile_warp=0, stored_coords=0)
     try:
         ref = fn().get()
+        first = remap_path(ctx)
+        fresh_ring_hint(ctx)
         ctx.set_tuning(ring_remap=2)
         got = fn().get()
+        second = remap_path(ctx)
     finally:
         ctx.set_tuning(**old)
+    assert only_gather(first), 'ring_remap=0 launched ' + path_names(first)
+    ring_rest = _lib.REMAP_PATH_RING | _lib.REMAP_PATH_REST
+    if ring:
+        assert second & ~_lib.REMAP_PATH_FRAMES_INNER == ring_rest, 'ring_remap=2 launched ' + path_names(second)
+    else:
+        assert only_gather(second), 'ring_remap=2 launched ' + path_names(second)
     return ref, got
 
 
@@ -145,7 +163,7 @@ def test_ring_remap_other_dtypes_take_the_gather_kernel(ia):
     dmx, dmy = ctx.to_device(mx), ctx.to_device(my)
     for dt in (np.uint16, np.float64):
         d_src = ctx.to_device(frames(n, h, w, dt) if dt == np.uint16 else frames(n, h, w).astype(dt))
-        ref, got = both(ia, lambda: ops.remap(d_src, dmx, dmy, 'cubic'))
+        ref, got = both(ia, lambda: ops.remap(d_src, dmx, dmy, 'cubic'), ring=False)
         assert np.array_equal(ref, got)
 
 

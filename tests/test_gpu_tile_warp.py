@@ -8,8 +8,10 @@ outside the source and not finite.
 import numpy as np
 import pytest
 
+from imgprocessor_amd import _lib
+
 from .conftest import assert_close
-from .gpu_helpers import frames, same_bits
+from .gpu_helpers import frames, only_gather, path_names, remap_path, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -34,18 +36,36 @@ def rot_persp(h, w, deg, persp=(1e-4, 5e-5), shift=(0.0, 0.0), zoom=1.0):
     return P @ R
 
 
-def both(ia, src, M, shape, interp, border='constant', cval=0.25):
-    """the same warp on the gather / ring kernels (tile_warp = 0) and on the tile kernel (2)"""
-    from imgprocessor_amd import ops
+def ran(ctx, tw, bit, declined=False):
+    """after a call of a hand-written tile_warp = 0 / 2 loop: the knob-off call launched no tile kernel, the
+    knob-on call the one the test is about and nothing else (declined: a call beyond what the tile shapes
+    hold, which must not have launched one)"""
+    p, tiles = remap_path(ctx), _lib.REMAP_PATH_TILE | _lib.REMAP_PATH_TILE_MAP
+    assert (p == bit) if tw and not declined else not p & tiles, 'tile_warp=%d launched %s' % (tw, path_names(p))
+
+
+def both(ia, src, M, shape, interp, border='constant', cval=0.25, tile=True):
+    """the same warp on the gather kernel alone (tile_warp = 0; ring kernel and stored coordinates off)
+    and on the tile kernel (2) - with the evidence of what ran (read-only "remap_path"): the first call
+    launched the gather kernel and nothing else, the second the tile kernel and nothing else.
+    tile=False: a homography no tile shape covers, which must NOT have launched it."""
+    from imgprocessor_amd import ops, _lib
     ctx = ia.default_context(0)
     d = ctx.to_device(src)
-    out = []
+    out, paths = [], []
+    old = ctx.set_tuning(ring_remap=0, stored_coords=0)
     try:
         for tw in (0, 2):
             ctx.set_tuning(tile_warp=tw)
             out.append(ops.warp_perspective(d, M, shape, interp, border, border_value=cval).get())
+            paths.append(remap_path(ctx))
     finally:
-        ctx.set_tuning(tile_warp=1)
+        ctx.set_tuning(tile_warp=1, **old)
+    assert only_gather(paths[0]), 'tile_warp=0 launched ' + path_names(paths[0])
+    if tile:
+        assert paths[1] == _lib.REMAP_PATH_TILE, 'tile_warp=2 launched ' + path_names(paths[1])
+    else:
+        assert only_gather(paths[1]), 'tile_warp=2 launched ' + path_names(paths[1])
     return out
 
 
@@ -99,19 +119,28 @@ def test_coordinates_outside_the_source_and_not_finite(ia):
     h, w = 120, 180
     src = frames(2, h, w)
     cases = {
-        'far outside': np.array([[1.0, 0, 5000.0], [0, 1.0, -3000.0], [0, 0, 1.0]]),
+        # (was 5000 / -3000: nothing of the source in sight, which the host hands back before any tile runs -
+        # the case had compared the gather kernel with itself; now one corner of the result sees the source,
+        # every other tile looks wholly outside)
+        'far outside': np.array([[1.0, 0, 150.0], [0, 1.0, -100.0], [0, 0, 1.0]]),
         'half outside': np.array([[1.0, 0.2, -90.0], [-0.2, 1.0, 60.0], [0, 0, 1.0]]),
         'horizon in the picture': np.array([[1.0, 0, 0], [0, 1.0, 0], [0.02, 0.0, -1.0]]),
-        'huge zoom out': np.array([[40.0, 0, 0], [0, 40.0, 0], [0, 0, 1.0]]),
+        # (was 40: boxes wider than the 128 columns of any tile shape, handed back as well; 3 is what the
+        # narrowest tile, 32 px, still holds)
+        'huge zoom out': np.array([[3.0, 0, 0], [0, 3.0, 0], [0, 0, 1.0]]),
         # boxes of 120-135 columns: around the 128 the kernel's fill covers (found by tools/fuzz_paths.py)
         'zoom out 1.85': np.array([[1.85, 0.03, -70.0], [-0.03, 1.85, -40.0], [0, 0, 1.0]]),
         'zoom out 2': np.array([[1.99, -0.067, -80.0], [0.069, 1.999, -50.0], [0, 0, 1.0]]),
         'degenerate': np.array([[1.0, 0, 0], [0, 1.0, 0], [0, 0, 0.0]]),
     }
+    # what the host must hand back to the gather kernel before any tile runs (tile_warp_box: a denominator that
+    # changes sign or vanishes) - "remap_path" showed that these two had compared the gather kernel with itself;
+    # no input of theirs can reach a tile, so they stay as the proof that they are handed back
+    declined = ('horizon in the picture', 'degenerate')
     for name, M in cases.items():
         for interp in ('linear', 'cubic', 'lanczos4'):
             for border in ('constant', 'replicate', 'wrap'):
-                ref, got = both(ia, src, M, (h, w), interp, border)
+                ref, got = both(ia, src, M, (h, w), interp, border, tile=name not in declined)
                 same_bits(got, ref, '%s %s %s' % (name, interp, border))
 
 
@@ -189,6 +218,7 @@ def test_uint16_frames_in_opencvs_16u_arithmetic(ia, oracle, interp):
                     for tw in (0, 2):
                         ctx.set_tuning(tile_warp=tw)
                         out.append(ops.warp_perspective(d, M, (h + 5, w - 3), interp, border, border_value=1000).get())
+                        ran(ctx, tw, _lib.REMAP_PATH_TILE)
                 finally:
                     ctx.set_tuning(tile_warp=1)
                 assert np.array_equal(out[0], out[1]), '%s %s %g deg: tile kernel differs from the gather kernel' % (
@@ -252,13 +282,17 @@ def test_small_tiles_where_the_picture_shrinks(ia, case):
     d = ctx.to_device(src)
     trapezoid = np.array([[1.0, 0.35, -70.0], [0.02, 1.9, -150.0], [0.0, 0.0022, 1.0]])   # far side 2x denser
     Ms = [rot_persp(h, w, 12.0, zoom=z) for z in (1.5, 2.2, 3.4, 4.6)] + [trapezoid]
-    for M in Ms:
+    for k, M in enumerate(Ms):
         for border in ('constant', 'reflect'):
             out = []
             try:
                 for tw in (0, 2):
                     ctx.set_tuning(tile_warp=tw)
                     out.append(ops.warp_perspective(d, M, (h - 20, w + 30), interp, border, border_value=3).get())
+                    # "beyond that": a box has at most 128 columns.  Shrunk 4.6 times the narrowest tile, 32 px,
+                    # spans 147; shrunk 3.4 times under 12 degrees about 118, which the 8 taps of Lanczos4 take
+                    # past the limit and the 2 or 4 of the others do not.  Every other call runs the tile kernel
+                    ran(ctx, tw, _lib.REMAP_PATH_TILE, declined=k == 3 or (k == 2 and interp == 'lanczos4'))
             finally:
                 ctx.set_tuning(tile_warp=1)
             assert np.array_equal(out[0].view(np.uint8), out[1].view(np.uint8)), \
@@ -300,6 +334,7 @@ def test_map_remaps_on_the_tile_kernel(ia, oracle, interp):
                     for tw in (0, 2):
                         ctx.set_tuning(tile_warp=tw)
                         out.append(ops.remap(d, dmx, dmy, interp, border, 0.25).get())
+                        ran(ctx, tw, _lib.REMAP_PATH_TILE_MAP)
                 finally:
                     ctx.set_tuning(tile_warp=1)
                 same_bits(out[1], out[0], '%s %s %s %dx%d' % (mname, interp, border, h, w))
@@ -324,8 +359,10 @@ def test_maps_that_need_more_than_the_reserve(ia):
         try:
             ctx.set_tuning(tile_warp=0)
             ref = ops.remap(d, dmx, dmy, interp, 'reflect').get()
+            ran(ctx, 0, _lib.REMAP_PATH_TILE_MAP)
             ctx.set_tuning(tile_warp=2)
             same_bits(ops.remap(d, dmx, dmy, interp, 'reflect').get(), ref, interp + ' forced')
+            ran(ctx, 2, _lib.REMAP_PATH_TILE_MAP)
         finally:
             ctx.set_tuning(tile_warp=1)
         for call in range(3):
