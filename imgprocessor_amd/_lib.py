@@ -41,6 +41,9 @@ STAT_MEDIAN, STAT_NANMEDIAN, STAT_MEAN, STAT_NANMEAN = range(4)
 # ipa_nlf_kind of ipa_nlf_threshold_dev
 NLF_BOUNDED_SQRT, NLF_CLIPPED_POLY, NLF_CONSTANT = range(3)
 
+# ipa_extremum_mode of ipa_strided_extremum_dev
+EXTREMUM_MEDIAN_MAX, EXTREMUM_MIN = range(2)
+
 # IPA_REMAP_PATH_* bits of the read-only tuning word "remap_path"
 (REMAP_PATH_GATHER, REMAP_PATH_REST, REMAP_PATH_RING, REMAP_PATH_TILE, REMAP_PATH_TILE_MAP,
  REMAP_PATH_STORED, REMAP_PATH_U8_LZ_LDS, REMAP_PATH_STRIP, REMAP_PATH_STRIP_INT, REMAP_PATH_LENS_MAP,
@@ -160,6 +163,13 @@ PROTOTYPES = {
     'ipa_stack_linregress_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _dp, _d, _d, _vp, _vp, _vp, _l],
     'ipa_dark_current_eval_dev': [_vp, _vp, _vp, _i, _i, _l, _d, _d, _vp, _i, _l],
     'ipa_cast_trunc_dev': [_vp, _vp, _i, _i, _l, _vp, _i, _l],
+    'ipa_stack_mean_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _vp, _l],
+    'ipa_luma_dev': [_vp, _vp, _i, _i, _l, _dp, _d, _vp, _l],
+    'ipa_strided_extremum_dev': [_vp, _vp, _i, _i, _i, _l, _i, _i, _i, _dp],
+    'ipa_flat_scale_dev': [_vp, _vp, _i, _i, _l, _vp, _l, _d, _i, _d, _i, _vp, _l],
+    'ipa_nlf_lower_mask_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _i, _dp, _d, _vp, _l],
+    'ipa_sens_shrink_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _i, _i, _vp, _l],
+    'ipa_sens_accumulate_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _vp, _i, _i, _l, _vp, _l, _i, _i],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

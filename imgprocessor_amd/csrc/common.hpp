@@ -198,6 +198,16 @@ int ipa_lens_map_cached(ipa_ctx* ctx, const double* K, const double* dist5, cons
 int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int sw, long src_pitch, const float* d_mapx,
                         const float* d_mapy, long map_pitch, void* d_dst, int dh, int dw, long dst_pitch, int n_frames,
                         long src_frame_stride, long dst_frame_stride, int interp, int border_mode, double border_value);
+// resize.hip -> flat.hip: the device tables of the separable resize of sh x sw into dh x dw (first-tap offsets and
+// `ks` float32 coefficients per destination column / row), in ctx->tab; those of the last call are reused
+struct ipa_resize_tabs {
+  const int* xofs;
+  const float* alpha;
+  const int* yofs;
+  const float* beta;
+  int xmax;   // columns from here on read one source pixel, times 1 (bilinear)
+};
+int ipa_resize_tables(ipa_ctx* ctx, int sh, int sw, int dh, int dw, int interp, int ks, ipa_resize_tabs* t);
 int ipa_plan_reserve(ipa_ctx* ctx, size_t bytes);                       // ctx->plan >= bytes (+50 % + 64 KiB); forgets plan_key
 int ipa_tab_upload(ipa_ctx* ctx, const void* host, size_t bytes, void** d);  // stream-ordered
 

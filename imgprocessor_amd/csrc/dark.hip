@@ -19,6 +19,7 @@
 // neither part of the reference tree nor installed where the fixtures are made.  The least-squares
 // definition in the header (means, centred sums in frame order, rms residual) is this project's.
 #include "common.hpp"
+#include "frame_args.hpp"
 #include "launch.hpp"
 #include "nlf_fn.hpp"
 
@@ -35,18 +36,6 @@ struct Times {
   double x[kDarkMaxT];
 };
 
-struct NlfParams {
-  int kind;
-  double p[5];
-};
-
-__device__ inline bool tile_px(int tiles_x, int h, int w, int& x, int& y) {
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  x = tx * 64 + (threadIdx.x & 63);
-  y = ty * 4 + (threadIdx.x >> 6);
-  return x < w && y < h;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kDarkThreads)
 pair_min_kernel(const T* __restrict__ f0, const T* __restrict__ f1, int h, int w, long pitch0, long pitch1,
@@ -61,22 +50,7 @@ nlf_threshold_kernel(const double* __restrict__ xs, int h, int w, long pitch, in
                      double nstd, double* __restrict__ thr, long thr_pitch) {
   int x, y;
   if (!tile_px(tiles_x, h, w, x, y)) return;
-  const double v = xs[(long)y * pitch + x];
-  double n;
-  if (f.kind == IPA_NLF_BOUNDED_SQRT) {
-    n = bounded_nlf(v, f.p[0], f.p[1], f.p[2]);
-  } else if (f.kind == IPA_NLF_CLIPPED_POLY) {
-    // np.clip: minimum(maximum(x, x0), x1), a NaN x passes through both
-    double c = v < f.p[3] ? f.p[3] : v;
-    c = c > f.p[4] ? f.p[4] : c;
-    // np.polyval's Horner loop, from y = 0
-    n = 0.0 * c + f.p[0];
-    n = n * c + f.p[1];
-    n = n * c + f.p[2];
-  } else {
-    n = f.p[0];
-  }
-  thr[(long)y * thr_pitch + x] = n * nstd;
+  thr[(long)y * thr_pitch + x] = nlf_eval(f, xs[(long)y * pitch + x]) * nstd;
 }
 
 struct RegressArgs {
@@ -88,12 +62,6 @@ struct RegressArgs {
   double* ascent;
   double* error;
   long out_pitch;
-};
-
-// PX adjacent pixels of a row, loaded and stored as one vector
-template <typename T, int PX>
-struct alignas(sizeof(T) * PX) PxVec {
-  T v[PX];
 };
 
 // pixels per lane: 4 or 8 bytes of every frame per lane where rows, frames and outputs are
@@ -265,44 +233,6 @@ cast_trunc_kernel(const double* __restrict__ in, int h, int w, long pitch, int t
   out[(long)y * out_pitch + x] = (O)in[(long)y * pitch + x];
 }
 
-bool known_dtype(int dtype) {
-  return dtype == IPA_U8 || dtype == IPA_U16 || dtype == IPA_F32 || dtype == IPA_F64;
-}
-
-struct Span {
-  const void* p;
-  size_t bytes;
-};
-Span span2d(const void* p, int h, int w, long pitch, size_t es) {
-  return {p, p ? ((size_t)(h - 1) * pitch + w) * es : 0};
-}
-bool overlap(Span a, Span b) {
-  if (!a.p || !b.p) return false;
-  const char *pa = (const char*)a.p, *pb = (const char*)b.p;
-  return pa < pb + b.bytes && pb < pa + a.bytes;
-}
-
-// f(T{}) for the element type of `dtype`; the caller has refused unknown dtypes
-template <typename F>
-int by_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case IPA_U8: return f((unsigned char)0);
-    case IPA_U16: return f((unsigned short)0);
-    case IPA_F32: return f(float{});
-    default: return f(double{});
-  }
-}
-
-// the checks every call shares; *tiles_x and *grid for the 64 x 4 tiles
-int frame_args(ipa_ctx* ctx, const char* what, int h, int w, int* tiles_x, unsigned* grid) {
-  IPA_REQUIRE(ctx, h > 0 && w > 0, "%s: empty image", what);
-  const long tx = (w + 63) / 64, ty = (h + 3) / 4;
-  IPA_REQUIRE(ctx, tx * ty <= 0x7fffffffL, "%s: image too large", what);
-  *tiles_x = (int)tx;
-  *grid = (unsigned)(tx * ty);
-  return IPA_OK;
-}
-
 }  // namespace
 }  // namespace ipa
 
@@ -341,8 +271,7 @@ int ipa_nlf_threshold_dev(ipa_ctx* ctx, const double* d_x, int h, int w, long pi
   int rc = frame_args(ctx, "nlf_threshold", h, w, &tiles_x, &grid);
   if (rc) return rc;
   IPA_REQUIRE(ctx, pitch >= w && thr_pitch >= w, "nlf_threshold: pitch smaller than width");
-  const int n_params = kind == IPA_NLF_BOUNDED_SQRT ? 3 : kind == IPA_NLF_CLIPPED_POLY ? 5
-                       : kind == IPA_NLF_CONSTANT ? 1 : 0;
+  const int n_params = nlf_param_count(kind);
   IPA_REQUIRE(ctx, n_params, "nlf_threshold: unknown kind %d", kind);
   // in place is fine - a lane reads its pixel before it writes it -, a partial overlap is not
   const bool same = d_x == d_thr && pitch == thr_pitch;

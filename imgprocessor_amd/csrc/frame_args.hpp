@@ -1,0 +1,61 @@
+// frame_args.hpp — what the streaming per-pixel units (dark.hip, flat.hip) share: the 64 x 4 tile of a
+// 256-thread workgroup, vectors of adjacent pixels, the argument checks of their entry points and the
+// dispatch on the element type.
+#pragma once
+#include "common.hpp"
+
+namespace ipa {
+
+// pixel of this lane on the 64 x 4 tile grid; false outside the image
+__device__ inline bool tile_px(int tiles_x, int h, int w, int& x, int& y) {
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  x = tx * 64 + (threadIdx.x & 63);
+  y = ty * 4 + (threadIdx.x >> 6);
+  return x < w && y < h;
+}
+
+// PX adjacent pixels of a row, loaded and stored as one vector
+template <typename T, int PX>
+struct alignas(sizeof(T) * PX) PxVec {
+  T v[PX];
+};
+
+inline bool known_dtype(int dtype) {
+  return dtype == IPA_U8 || dtype == IPA_U16 || dtype == IPA_F32 || dtype == IPA_F64;
+}
+
+struct Span {
+  const void* p;
+  size_t bytes;
+};
+inline Span span2d(const void* p, int h, long w, long pitch, size_t es) {
+  return {p, p ? ((size_t)(h - 1) * pitch + w) * es : 0};
+}
+inline bool overlap(Span a, Span b) {
+  if (!a.p || !b.p) return false;
+  const char *pa = (const char*)a.p, *pb = (const char*)b.p;
+  return pa < pb + b.bytes && pb < pa + a.bytes;
+}
+
+// f(T{}) for the element type of `dtype`; the caller has refused unknown dtypes
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case IPA_U8: return f((unsigned char)0);
+    case IPA_U16: return f((unsigned short)0);
+    case IPA_F32: return f(float{});
+    default: return f(double{});
+  }
+}
+
+// the checks every call shares; *tiles_x and *grid for the 64 x 4 tiles
+inline int frame_args(ipa_ctx* ctx, const char* what, int h, int w, int* tiles_x, unsigned* grid) {
+  IPA_REQUIRE(ctx, h > 0 && w > 0, "%s: empty image", what);
+  const long tx = (w + 63) / 64, ty = (h + 3) / 4;
+  IPA_REQUIRE(ctx, tx * ty <= 0x7fffffffL, "%s: image too large", what);
+  *tiles_x = (int)tx;
+  *grid = (unsigned)(tx * ty);
+  return IPA_OK;
+}
+
+}  // namespace ipa

@@ -53,18 +53,9 @@ __device__ inline double src_px(const NlfSrc& s, const void* img, long pitch, in
   return v - (s.bg ? s.bg[(long)y * s.bg_pitch + x] : s.bg_value);
 }
 
-// compare-exchange with numpy's NaN rule: a NaN reaches both outputs
-__device__ inline void cswap(double& a, double& b) {
-  const double lo = np_min(a, b), hi = np_max(a, b);
-  a = lo;
-  b = hi;
-}
-__device__ inline double med3(double a, double b, double c) {
-  return np_max(np_min(a, b), np_min(np_max(a, b), c));
-}
-
-// signal = median_filter(img, 3) or median_filter(0.5 * (img + img2), 3): rank 4 of the 9, the
-// edge pixel repeated.  A NaN in the window gives NaN (scipy's answer there is unspecified).
+// signal = median_filter(img, 3) or median_filter(0.5 * (img + img2), 3): rank 4 of the 9
+// (median9 of nlf_fn.hpp), the edge pixel repeated.  A NaN in the window gives NaN (scipy's answer
+// there is unspecified).
 template <typename T>
 __global__ void __launch_bounds__(kNlfThreads)
 nlf_signal_kernel(NlfSrc s, int h, int w, int tiles_x, double* __restrict__ out, long out_pitch) {
@@ -82,16 +73,8 @@ nlf_signal_kernel(NlfSrc s, int h, int w, int tiles_x, double* __restrict__ out,
       if (s.img2) v = 0.5 * (v + src_px<T>(s, s.img2, s.pitch2, yy, xx));
       c[i][j] = v;
     }
-    cswap(c[i][0], c[i][1]);
-    cswap(c[i][1], c[i][2]);
-    cswap(c[i][0], c[i][1]);
   }
-  // sorted columns: the median of 9 is the median of (largest minimum, median of the medians,
-  // smallest maximum)
-  const double lo = np_max(np_max(c[0][0], c[1][0]), c[2][0]);
-  const double mid = med3(c[0][1], c[1][1], c[2][1]);
-  const double hi = np_min(np_min(c[0][2], c[1][2]), c[2][2]);
-  out[(long)y * out_pitch + x] = med3(lo, mid, hi);
+  out[(long)y * out_pitch + x] = median9(c);
 }
 
 // ---------------------------------------------------------------- moments

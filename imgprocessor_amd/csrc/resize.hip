@@ -307,6 +307,41 @@ static int launch_separable(ipa_ctx* ctx, int ks, const void* src, long spitch, 
 
 using namespace ipa;
 
+// the tables of the last resize are still on the device (a sequence of frames of one shape:
+// building OpenCV's Lanczos4 coefficients for an 8K result costs the host ~0.2 ms)
+int ipa_resize_tables(ipa_ctx* ctx, int sh, int sw, int dh, int dw, int interp, int ks, ipa_resize_tabs* t) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const long key[5] = {sw, dw, sh, dh, interp};
+  const size_t b0 = up((size_t)dw * 4), b1 = up((size_t)dw * ks * 4), b2 = up((size_t)dh * 4),
+               b3 = up((size_t)dh * ks * 4);
+  int xmax = dw;
+  void* d = nullptr;
+  if (ctx->tab && ctx->resize_serial == ctx->tab_serial && ctx->resize_serial &&
+      memcmp(key, ctx->resize_key, sizeof key) == 0) {
+    d = ctx->tab;
+    xmax = ctx->resize_xmax;
+  } else {
+    std::vector<int> xofs, yofs;
+    std::vector<float> alpha, beta;
+    axis_tables(sw, dw, resize_scale(sw, dw), interp, ks, true, xofs, alpha, &xmax);
+    axis_tables(sh, dh, resize_scale(sh, dh), interp, ks, false, yofs, beta, nullptr);
+    std::vector<char> blob(b0 + b1 + b2 + b3);
+    memcpy(blob.data(), xofs.data(), xofs.size() * 4);
+    memcpy(blob.data() + b0, alpha.data(), alpha.size() * 4);
+    memcpy(blob.data() + b0 + b1, yofs.data(), yofs.size() * 4);
+    memcpy(blob.data() + b0 + b1 + b2, beta.data(), beta.size() * 4);
+    ctx->resize_serial = 0;
+    const int rc = ipa_tab_upload(ctx, blob.data(), blob.size(), &d);
+    if (rc) return rc;
+    memcpy(ctx->resize_key, key, sizeof key);
+    ctx->resize_serial = ctx->tab_serial;
+    ctx->resize_xmax = xmax;
+  }
+  const char* p = (const char*)d;
+  *t = {(const int*)p, (const float*)(p + b0), (const int*)(p + b0 + b1), (const float*)(p + b0 + b1 + b2), xmax};
+  return IPA_OK;
+}
+
 extern "C" {
 
 int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, long src_pitch,
@@ -365,42 +400,14 @@ int ipa_resize_dev(ipa_ctx* ctx, const void* d_src, int dtype, int sh, int sw, l
     IPA_UNSUPPORTED(ctx, "resize: interpolation %d (INTER_LINEAR 1, INTER_CUBIC 2, INTER_AREA 3, "
                          "INTER_LANCZOS4 4 are built)", interp);
   const int ks = interp == IPA_RESIZE_LINEAR ? 2 : (interp == IPA_RESIZE_CUBIC ? 4 : 8);
-  // the tables of the last resize are still on the device (a sequence of frames of one shape:
-  // building OpenCV's Lanczos4 coefficients for an 8K result costs the host ~0.2 ms)
-  const long key[5] = {sw, dw, sh, dh, interp};
-  const size_t b0 = up((size_t)dw * 4), b1 = up((size_t)dw * ks * 4), b2 = up((size_t)dh * 4),
-               b3 = up((size_t)dh * ks * 4);
-  int xmax = dw;
-  void* d = nullptr;
-  int rc = 0;
-  if (ctx->tab && ctx->resize_serial == ctx->tab_serial && ctx->resize_serial &&
-      memcmp(key, ctx->resize_key, sizeof key) == 0) {
-    d = ctx->tab;
-    xmax = ctx->resize_xmax;
-  } else {
-    std::vector<int> xofs, yofs;
-    std::vector<float> alpha, beta;
-    axis_tables(sw, dw, scale_x, interp, ks, true, xofs, alpha, &xmax);
-    axis_tables(sh, dh, scale_y, interp, ks, false, yofs, beta, nullptr);
-    std::vector<char> blob(b0 + b1 + b2 + b3);
-    memcpy(blob.data(), xofs.data(), xofs.size() * 4);
-    memcpy(blob.data() + b0, alpha.data(), alpha.size() * 4);
-    memcpy(blob.data() + b0 + b1, yofs.data(), yofs.size() * 4);
-    memcpy(blob.data() + b0 + b1 + b2, beta.data(), beta.size() * 4);
-    ctx->resize_serial = 0;
-    rc = ipa_tab_upload(ctx, blob.data(), blob.size(), &d);
-    if (rc) return rc;
-    memcpy(ctx->resize_key, key, sizeof key);
-    ctx->resize_serial = ctx->tab_serial;
-    ctx->resize_xmax = xmax;
-  }
+  ipa_resize_tabs t;
+  int rc = ipa_resize_tables(ctx, sh, sw, dh, dw, interp, ks, &t);
+  if (rc) return rc;
   rc = ipa_plan_reserve(ctx, (size_t)sh * dw * es);   // the horizontally resized rows
   if (rc) return rc;
-  const char* t = (const char*)d;
   return by_float(dtype, [&](auto f) {
     return launch_separable<decltype(f)>(ctx, ks, d_src, src_pitch, sh, sw, ctx->plan, d_dst, dst_pitch,
-                                         dh, dw, (const int*)t, (const float*)(t + b0), xmax,
-                                         (const int*)(t + b0 + b1), (const float*)(t + b0 + b1 + b2));
+                                         dh, dw, t.xofs, t.alpha, t.xmax, t.yofs, t.beta);
   });
 }
 

@@ -16,6 +16,9 @@ from .ops_nlf import nlf_signal, nlf_moments, nlf_bins, snr_map, snr_bg_median  
 # the dark-current family lives in ops_dark.py
 from .ops_dark import (pair_min, nlf_threshold, stack_linregress, dark_current_eval,  # noqa: F401
                        cast_trunc, nlf_params)
+# the flat-field family lives in ops_flat.py
+from .ops_flat import (stack_mean, luma, strided_median_max, strided_min, flat_scale,  # noqa: F401
+                       nlf_lower_mask, sens_shrink, sens_accumulate)
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

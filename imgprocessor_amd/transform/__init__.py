@@ -4,3 +4,4 @@ from .rotate import rotate  # noqa: F401
 from .simplePerspectiveTransform import simplePerspectiveTransform  # noqa: F401
 from .polarTransform import (linearToPolar, polarToLinear, linearToPolarMaps,  # noqa: F401
                              polarToLinearMaps)
+from .imgAverage import imgAverage  # noqa: F401

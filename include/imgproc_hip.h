@@ -799,6 +799,72 @@ int ipa_dark_current_eval_dev(ipa_ctx* ctx, const double* d_offset, const double
 int ipa_cast_trunc_dev(ipa_ctx* ctx, const double* d_in, int h, int w, long pitch, void* d_out, int out_dtype,
                        long out_pitch);
 
+/* ---------------------------------------------------------------- flat field calibration */
+/* The frame passes of camera/flatField/flatFieldFromCloseDistance.py and camera/flatField/
+ * sensitivity.py.  Frames are uint8 / uint16 / float32 / float64 (IPA_ERR_UNSUPPORTED otherwise),
+ * pitches in elements; all arithmetic is float64, every operation correctly rounded and unfused. */
+
+/* replaces transform/imgAverage.py:14-21 (`out = float(i0); out += float(i); out /= len(images)`):
+ * d_out (float64) = the sum of the n frames in frame order, divided by n.  Any n >= 1.  A colour
+ * stack (n, h, w, 3) is served as (n, h, 3 * w).  Stack and result must not overlap. */
+int ipa_stack_mean_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int n, int h, int w, long pitch,
+                       long frame_stride, double* d_out, long out_pitch);
+
+/* replaces toGray of transformations.py:126-135 (np.average(img, axis=-1, weights=(0.299, 0.587,
+ * 0.114))) on an interleaved float64 frame (h, w, 3), `pitch` elements per row (>= 3 * w):
+ * d_out = ((r * wgt[0] + g * wgt[1]) + b * wgt[2]) / wsum.  wgt: 3 doubles (HOST); wsum is the
+ * caller's, computed as numpy computes wgt.sum().  Not in place. */
+int ipa_luma_dev(ipa_ctx* ctx, const double* d_img, int h, int w, long pitch, const double* wgt, double wsum,
+                 double* d_out, long out_pitch);
+
+typedef enum {
+  IPA_EXTREMUM_MEDIAN_MAX = 0, /* median_filter(a[::sy, ::sx], 3).max(), float64 frames */
+  IPA_EXTREMUM_MIN = 1         /* a[::sy, ::sx].min() */
+} ipa_extremum_mode;
+/* replaces `median_filter(img[::10, ::10], 3).max()` of camera/flatField/flatFieldFromCloseDistance.py
+ * :36 and :91 (scipy's 'reflect' border on the strided grid: the edge sample repeated) and the
+ * `img[::s0 // 10, ::s1 // 10].min()` of its sort key (:62).  *result (HOST) is the extremum as a
+ * double - every value of the four element types is one -, a NaN among the samples wins as in
+ * numpy.  Per-workgroup partial extrema and a second small pass, no float atomics; the call
+ * synchronises.  step_y, step_x >= 1. */
+int ipa_strided_extremum_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, int step_y,
+                             int step_x, int mode, double* result);
+
+/* replaces `img -= bg` and `img /= mx` of camera/flatField/flatFieldFromCloseDistance.py:34-37 and
+ * `ma / mx` of :96: d_out = (d_img - bg) / div over float64 frames, or one of the two steps
+ * (subtract = 0 / divide = 0).  bg is d_bg (float64, bg_pitch) or, where that is NULL, bg_value.
+ * d_out may be d_img itself (same pitch). */
+int ipa_flat_scale_dev(ipa_ctx* ctx, const double* d_img, int h, int w, long pitch, const double* d_bg,
+                       long bg_pitch, double bg_value, int subtract, double div, int divide, double* d_out,
+                       long out_pitch);
+
+/* replaces `thresh = det.noSTE - nlf(det.noSTE) * nstd; mask = i > thresh` of camera/flatField/
+ * flatFieldFromCloseDistance.py:80-81: d_mask (uint8) = frame > avg - nlf(avg) * nstd, compared in
+ * float64, 0 where either side is NaN.  kind / params as in ipa_nlf_threshold_dev.  The mask is
+ * what ipa_ste_dev takes as d_mask. */
+int ipa_nlf_lower_mask_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                           const double* d_avg, long avg_pitch, int kind, const double* params, double nstd,
+                           unsigned char* d_mask, long mask_pitch);
+
+/* replaces `fastMean(median_filter(i - bg, 3))` of camera/flatField/sensitivity.py:21-23 up to the
+ * small image: d_small (float64, dh x dw) = cv2.resize(median_filter(frame - bg, 3), (dw, dh),
+ * INTER_AREA) as ipa_resize_dev computes it.  bg as in ipa_nlf_signal_dev.  Where h = isy * dh and
+ * w = isx * dw this is one kernel that writes no frame-sized intermediate: the medians of a block
+ * are summed row-major in groups of four, times (float)(1 / area).  Otherwise the median frame goes
+ * through the context's workspace and ipa_resize_dev shrinks it.  Enlarging is IPA_ERR_UNSUPPORTED. */
+int ipa_sens_shrink_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                        const double* d_bg, long bg_pitch, double bg_value, int dh, int dw, double* d_small,
+                        long small_pitch);
+
+/* replaces `i /= smooth; out += i` and `out /= n + 1` of camera/flatField/sensitivity.py:24-29:
+ * d_acc (float64) = (frame - bg) / up(small) where first, d_acc + that otherwise, then / n_last
+ * where n_last > 0.  up(small) is cv2.resize(small, (w, h), INTER_LINEAR) as ipa_resize_dev
+ * computes it, evaluated per pixel: the two horizontal blends, each rounded to float64, then the
+ * vertical one.  d_acc must not overlap the frame, bg or small. */
+int ipa_sens_accumulate_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                            const double* d_bg, long bg_pitch, double bg_value, const double* d_small, int dh,
+                            int dw, long small_pitch, double* d_acc, long acc_pitch, int first, int n_last);
+
 #ifdef __cplusplus
 }
 #endif
