@@ -170,6 +170,9 @@ PROTOTYPES = {
     'ipa_nlf_lower_mask_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _i, _dp, _d, _vp, _l],
     'ipa_sens_shrink_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _i, _i, _vp, _l],
     'ipa_sens_accumulate_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _vp, _i, _i, _l, _vp, _l, _i, _i],
+    'ipa_tss_event_length_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _dp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l,
+                                 _vp, _l, _l],
+    'ipa_tss_finish_dev': [_vp, _vp, _vp, _i, _i, _l, _l, _vp, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

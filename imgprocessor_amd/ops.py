@@ -19,6 +19,8 @@ from .ops_dark import (pair_min, nlf_threshold, stack_linregress, dark_current_e
 # the flat-field family lives in ops_flat.py
 from .ops_flat import (stack_mean, luma, strided_median_max, strided_min, flat_scale,  # noqa: F401
                        nlf_lower_mask, sens_shrink, sens_accumulate)
+# the signal-stability family lives in ops_tss.py
+from .ops_tss import tss_event_length, tss_finish  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -865,6 +865,55 @@ int ipa_sens_accumulate_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, i
                             const double* d_bg, long bg_pitch, double bg_value, const double* d_small, int dh,
                             int dw, long small_pitch, double* d_acc, long acc_pitch, int first, int n_last);
 
+/* What uncertainty/temporalSignalStability.py needs after its line fit (ipa_stack_linregress_dev
+ * with mx_intensity = inf, min_ascent = 0).  Frames are uint8 / uint16 / float32 / float64, pitches
+ * and frame strides in elements; all arithmetic is float64, every operation correctly rounded and
+ * unfused. */
+
+/* replaces uncertainty/temporalSignalStability.py:56-66 and _calcAvgLen (:83-107) in one launch:
+ * fn_imgs, diff, median_filter(diff, 5) over the (T, h, w) cube, evt = |.| > 0.5 * error and the
+ * average run length of the events along the frames.  times: T doubles (HOST); d_offset, d_ascent,
+ * d_error: float64 planes of one pitch (plane_pitch).  Per voxel, in this order:
+ *   r[k](y, x)  = (double)img[k](y, x) - (offset(y, x) + times[k] * ascent(y, x))
+ *   c           = 0.5 * error(y0, x0)                       the threshold of the CENTRE pixel
+ *   plus[k]     = #{r[k'](y, x) >  c},  minus[k] = #{r[k'](y, x) < -c}  over the 5 x 5 x 5 window
+ *                 around (k, y0, x0), indices beyond the cube taken by scipy's `reflect`
+ *                 (d c b a | a b c d) on all three axes, reflected as often as it takes
+ *   evt[k]      = plus[k] >= 63 || minus[k] >= 63
+ * The median of 125 finite values is the value of rank 62 (from 0): it is above c exactly when at
+ * least 63 values are, below -c exactly when at least 63 are below -c, so evt equals
+ * |median_filter(diff, 5)| > 0.5 * error bit for bit without the median being formed.  A residual
+ * beyond the centre pixel is formed with ITS pixel's offset and ascent.  Then per pixel, along k:
+ *   nvals = #{evt[k]};  nclusters = #runs of consecutive event frames
+ *   avlen = nclusters == 0 ? 0 : (double)nvals / (double)nclusters
+ * d_avlen: float64.  d_zero_mask (uint8, may be NULL): 1 where avlen == 0, the mask of :69.
+ * d_events (uint8 (T, h, w), ev_pitch, ev_frame_stride; may be NULL): evt itself.
+ * NaN: with a NaN sample in a window scipy's own selection depends on the order of the values;
+ * the result is undefined here too.  A NaN error gives no event (every comparison is false).
+ * 2 <= T <= 64 (above, or another dtype: IPA_ERR_UNSUPPORTED; below: IPA_ERR_BAD_ARG); any
+ * h, w >= 1.  Null pointers, an empty image, a pitch smaller than the width, frames that overlap
+ * and an output that overlaps an input or another output are IPA_ERR_BAD_ARG.  Nothing is written
+ * on refusal.  Every frame value is read once per 64 x 16 tile (and its 2-pixel halo); no
+ * workspace, nothing of size T*h*w but d_events. */
+int ipa_tss_event_length_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int T, int h, int w, long pitch,
+                             long frame_stride, const double* times, const double* d_offset,
+                             const double* d_ascent, const double* d_error, long plane_pitch, double* d_avlen,
+                             long avlen_pitch, unsigned char* d_zero_mask, long mask_pitch,
+                             unsigned char* d_events, long ev_pitch, long ev_frame_stride);
+
+/* replaces uncertainty/temporalSignalStability.py:72-78, the tail after maskedFilter.  d_mean: the
+ * mean-filtered event length (float64, NaN where masked); d_mask: uint8, non-zero where the raw
+ * event length was 0.  With the edge pixel repeated beyond the image in every step:
+ *   m1 = 3 x 3 maximum of mask                      maximum_filter(i, 3)
+ *   a2 = m1 ? 0 : mean                              avlen[i] = 0
+ *   a3 = 3 x 3 maximum of a2                        maximum_filter(avlen, 3)
+ *   out = a3 == 0 ? 0 : rank 4 of the 3 x 3 of a3   median_filter(avlen, 3); avlen[i] = 0
+ * Selection only: every output value is an input value or 0.  a2 is finite when every unmasked
+ * pixel of d_mean is (the masked mean averages at least the pixel itself); a NaN there is
+ * undefined.  Not in place (IPA_ERR_BAD_ARG), any h, w >= 1. */
+int ipa_tss_finish_dev(ipa_ctx* ctx, const double* d_mean, const unsigned char* d_mask, int h, int w, long pitch,
+                       long mask_pitch, double* d_out, long out_pitch);
+
 #ifdef __cplusplus
 }
 #endif
