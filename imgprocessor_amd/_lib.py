@@ -173,6 +173,10 @@ PROTOTYPES = {
     'ipa_tss_event_length_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _dp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l,
                                  _vp, _l, _l],
     'ipa_tss_finish_dev': [_vp, _vp, _vp, _i, _i, _l, _l, _vp, _l],
+    'ipa_ovs_object_dev': [_vp, _vp, _i, _i, _l, _vp, _i, _i, _i, _i, _l, _l, _dp, _vp, _l, _vp, _l],
+    'ipa_ovs_flatfield_dev': [_vp, _vp, _l, _vp, _i, _i, _i, _i, _l, _l, _vp, _l, _l, _dp, _vp, _i, _i, _l,
+                              _vp, _l, _i, _vp, _i, _l],
+    'ipa_masked_running_mean_dev': [_vp, _vp, _l, _vp, _l, _vp, _i, _l, _vp, _l, _i, _i],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

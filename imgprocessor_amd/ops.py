@@ -21,6 +21,8 @@ from .ops_flat import (stack_mean, luma, strided_median_max, strided_min, flat_s
                        nlf_lower_mask, sens_shrink, sens_accumulate)
 # the signal-stability family lives in ops_tss.py
 from .ops_tss import tss_event_length, tss_finish  # noqa: F401
+# the object / vignetting separation family lives in ops_ovs.py
+from .ops_ovs import ovs_object, ovs_flatfield, masked_running_mean_update  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

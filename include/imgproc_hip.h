@@ -914,6 +914,55 @@ int ipa_tss_event_length_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int T
 int ipa_tss_finish_dev(ipa_ctx* ctx, const double* d_mean, const unsigned char* d_mask, int h, int w, long pitch,
                        long mask_pitch, double* d_out, long out_pitch);
 
+/* ---- object / vignetting separation (csrc/ovs.hip) --------------------------------------------
+ * The refinement loop of camera/flatField/vignettingFromRandomSteps.py (ObjectVignettingSeparation
+ * .__next__, :238-282) for fitted images and homographies the caller supplies.  d_fits: n images on
+ * the object grid (oh x ow), uint8 / uint16 / float32 / float64, fit_pitch and fit_frame_stride in
+ * elements.  mats: n destination -> source matrices, 9 row-major doubles each (HOST; they travel
+ * through the context's table buffer, nothing is allocated per call).  A sample is what
+ * ipa_warp_perspective_dev computes on a float64 image with IPA_INTER_LINEAR | IPA_INTER_Q5,
+ * IPA_BORDER_CONSTANT, 0.0 - the same device functions - so the results equal the composed calls
+ * bit for bit.  The running mean is MaskedMovingAverage.update as the project restates it
+ * (tests/golden/gen_ste_golden.py): per accepted value x, n += 1; avg = n == 1 ? x : avg + (x - avg) / n.
+ * All arithmetic is float64, every division IEEE, nothing fused beyond the sampler's own fma.
+ * 1 <= n <= 64 (0: IPA_ERR_BAD_ARG, above: IPA_ERR_UNSUPPORTED); another dtype is
+ * IPA_ERR_UNSUPPORTED; null pointers, an empty image, a pitch smaller than the width, frames that
+ * overlap and an output that overlaps an input or another output are IPA_ERR_BAD_ARG.  Nothing is
+ * written on refusal; padding is never written. */
+
+/* replaces camera/flatField/vignettingFromRandomSteps.py:241-249 in one launch: per object pixel,
+ * for k = 0 .. n-1 in order, w = sample(ff, mats[k] * (x, y, 1)); where w != 0 (a NaN is accepted,
+ * as in numpy) the running mean takes (double)fit[k](y, x) / w.  d_ff: float64 fh x fw, at most
+ * 2^28 elements; d_obj: float64, d_count: int32, both oh x ow - the average and the number of
+ * accepted values (0 and 0 where none was).  No warped frame is written anywhere. */
+int ipa_ovs_object_dev(ipa_ctx* ctx, const double* d_ff, int fh, int fw, long ff_pitch, const void* d_fits, int dtype,
+                       int n, int oh, int ow, long fit_pitch, long fit_frame_stride, const double* mats,
+                       double* d_obj, long obj_pitch, int* d_count, long count_pitch);
+
+/* replaces camera/flatField/vignettingFromRandomSteps.py:253-265 in one launch: per flat-field
+ * pixel, for k in order, v = sample(div[k], mats[k] * (x, y, 1)) of the image div[k] that is never
+ * stored - NaN where d_masks[k] (uint8, oh x ow per frame) is set, (double)fit[k] / obj elsewhere,
+ * each tap formed when it is read; taps beyond the frame are the constant 0 and a footprint wholly
+ * outside gives 0 without a division.  Then np.nan_to_num (NaN -> 0, +-inf -> +-DBL_MAX), and the
+ * running mean takes v where v != 0.  d_ff: float64, d_count: int32, both fh x fw.
+ * clip01 != 0 stores np.clip(avg, 0, 1) (NaN stays) - the flat field of the next step, :278.
+ * d_sub (may be NULL): float64 ceil(fh / sub_step) x ceil(fw / sub_step), the UNCLIPPED average at
+ * every sub_step-th pixel of every sub_step-th row, what the residuum of :269-270 reads. */
+int ipa_ovs_flatfield_dev(ipa_ctx* ctx, const double* d_obj, long obj_pitch, const void* d_fits, int dtype, int n,
+                          int oh, int ow, long fit_pitch, long fit_frame_stride, const unsigned char* d_masks,
+                          long mask_pitch, long mask_frame_stride, const double* mats, double* d_ff, int fh, int fw,
+                          long ff_pitch, int* d_count, long count_pitch, int clip01, double* d_sub, int sub_step,
+                          long sub_pitch);
+
+/* one MaskedMovingAverage.update(data, mask) (camera/flatField/vignettingFromRandomSteps.py:146-151,
+ * the initial flat field) on device-resident state: where d_mask (uint8; NULL: everywhere) is set,
+ * n += 1; x = (double)data; avg = n == 1 ? x : avg + (x - avg) / n.  d_avg: float64, d_n: int32,
+ * updated in place; d_data: uint8 / uint16 / float32 / float64.  The state must not overlap the
+ * inputs (IPA_ERR_BAD_ARG). */
+int ipa_masked_running_mean_dev(ipa_ctx* ctx, double* d_avg, long avg_pitch, int* d_n, long n_pitch, const void* d_data,
+                                int dtype, long data_pitch, const unsigned char* d_mask, long mask_pitch, int h,
+                                int w);
+
 #ifdef __cplusplus
 }
 #endif
