@@ -39,6 +39,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .. import ops, ops_dark
+from .._staging import frame_stack
 from ..device import DeviceArray, default_context
 from ..features.SingleTimeEffectDetection import SingleTimeEffectDetection
 from .NoiseLevelFunction import oneImageNLF
@@ -178,7 +179,8 @@ def _averages(exposuretimes, imgs, fit=False):
             stack.frame(n).copy_from(group[0] if dev else ctx.to_device(group[0]))
             continue
         # a host group goes up once, as one stack
-        d = SingleTimeEffectDetection._stack_dev(group) if dev else ctx.to_device(np.stack(group))
+        d = frame_stack('getDarkCurrentAverages', group)
+        d = d if dev else ctx.to_device(d)
         m = DarkCurrentMap([d.frame(k) for k in range(2)])
         for k in range(2, len(group)):
             m.addImg(d.frame(k))

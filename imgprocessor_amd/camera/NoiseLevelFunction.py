@@ -28,7 +28,8 @@ Differences from the reference, all at its undefined corners:
 """
 import numpy as np
 
-from .. import ops, ops_nlf
+from .. import ops
+from .._staging import _f64_frame, _frame_pair
 
 # factor root-mean-square to average-absolute-deviation
 F_RMS2AAD = (2 / np.pi) ** -0.5
@@ -205,11 +206,11 @@ def calcNLF(img, img2=None, signal=None, mn_mx_nbins=None, x=None, averageFn='AA
 
 def _calc(img, img2, signal, mn_mx_nbins, x, averageFn, signalFromMultipleImages, bg):
     """calcNLF on frames read as `frame - bg` (what SNR hands to oneImageNLF)"""
-    dev, ctx, d_img, d_img2, _, _ = ops_nlf._nlf_frames('calcNLF', img, img2, None, (signal, bg))
+    dev, ctx, d_img, d_img2, _, _ = _frame_pair('calcNLF', img, img2, None, (signal, bg))
     if signal is None:
         d_sig = ops.nlf_signal(d_img, d_img2, bg=bg)
     else:
-        d_sig = ops_nlf._f64_frame('calcNLF', 'signal', signal, d_img.shape, ctx)
+        d_sig = _f64_frame('calcNLF', 'signal', signal, d_img.shape, ctx)
     if img2 is None:
         factor = 1.0 if signalFromMultipleImages else F_NOISE_WITH_MEDIAN
     else:

@@ -30,8 +30,8 @@ import numbers
 
 import numpy as np
 
-from ... import ops, ops_flat
-from ...ops_nlf import _nlf_host
+from ... import ops
+from ..._staging import _px_host, check_dev_frames, gather_dev
 from ...device import DeviceArray, default_context
 from ...features.SingleTimeEffectDetection import SingleTimeEffectDetection
 from ...utils.getBackground2 import getBackground2
@@ -60,7 +60,7 @@ def _stack(name, images, ndims):
         if any(dev) and not all(dev):
             raise TypeError('%s: mix of host and device frames' % name)
         if st and dev[0]:
-            ops_flat.check_dev_frames(name, st)
+            check_dev_frames(name, st)
         elif st:
             st = np.stack([np.asarray(f) for f in st])
         n, shape = len(st), (tuple(st[0].shape) if len(st) else ())
@@ -78,7 +78,7 @@ def _on_device(ctx, st):
     """what _stack returned as one DeviceArray"""
     if isinstance(st, DeviceArray):
         return st
-    return ops_flat.gather_dev('frames', st) if isinstance(st, list) else ctx.to_device(_nlf_host(st))
+    return gather_dev('frames', st) if isinstance(st, list) else ctx.to_device(_px_host(st))
 
 
 def _view(d, shape, k=0):

@@ -24,9 +24,8 @@ supplies.  The three functions stay as they are for callers that warp single ima
 import numpy as np
 
 from ... import ops
-from ..._staging import _ctx_of
+from ..._staging import PIXEL_DTYPES, _ctx_of, _px_host
 from ...device import DeviceArray
-from ...ops_nlf import NLF_DTYPES, _nlf_host
 
 
 def _warp(img, H, shape, ctx=None):
@@ -173,8 +172,8 @@ class ObjectVignettingSeparation(object):
             raise NotImplementedError('addFit: at most %d fitted images' % MAX_FITS)
         dev = isinstance(fit, DeviceArray)
         ctx = self._context(fit, mask, img, img_mask)
-        d_fit = fit if dev else ctx.to_device(_nlf_host(fit))
-        if d_fit.dtype not in NLF_DTYPES:
+        d_fit = fit if dev else ctx.to_device(_px_host(fit))
+        if d_fit.dtype not in PIXEL_DTYPES:
             raise TypeError('addFit: fitted images are uint8 / uint16 / float32 / float64 (got %s)' % d_fit.dtype)
         if self.fits and d_fit.dtype != self.fits[0].dtype:
             raise TypeError('addFit: all fitted images must have one element type (%s, got %s)'

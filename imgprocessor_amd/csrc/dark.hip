@@ -299,12 +299,10 @@ int ipa_stack_linregress_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int T
   IPA_REQUIRE(ctx, frame_stride >= (long)(h - 1) * pitch + w, "stack_linregress: frames overlap");
   if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "stack_linregress: frames are uint8 / uint16 / float32 / float64 (got dtype %d)", dtype);
-  const Span st = {d_stack, ((size_t)(T - 1) * frame_stride + (size_t)(h - 1) * pitch + w) * ipa_dtype_size(dtype)};
   const Span spans[] = {span2d(d_offset, h, w, out_pitch, 8), span2d(d_ascent, h, w, out_pitch, 8),
-                        span2d(d_error, h, w, out_pitch, 8), st};
-  for (int i = 0; i < 3; i++)
-    for (int j = i + 1; j < 4; j++)
-      IPA_REQUIRE(ctx, !overlap(spans[i], spans[j]), "stack_linregress: stack and outputs overlap");
+                        span2d(d_error, h, w, out_pitch, 8),
+                        span_stack(d_stack, T, h, w, pitch, frame_stride, ipa_dtype_size(dtype))};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 3), "stack_linregress: stack and outputs overlap");
   Times t;
   double lo = times[0], hi = times[0];
   for (int k = 0; k < kDarkMaxT; k++) {

@@ -343,7 +343,7 @@ int ipa_stack_mean_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int n, int 
   if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "stack_mean: frames are uint8 / uint16 / float32 / float64 (got dtype %d)", dtype);
   const size_t es = ipa_dtype_size(dtype);
-  const Span st = {d_stack, ((size_t)(n - 1) * frame_stride + (size_t)(h - 1) * pitch + w) * es};
+  const Span st = span_stack(d_stack, n, h, w, pitch, frame_stride, es);
   IPA_REQUIRE(ctx, !overlap(st, span2d(d_out, h, w, out_pitch, 8)), "stack_mean does not run in place");
   return by_dtype(dtype, [&](auto e) {
     using E = decltype(e);

@@ -1,6 +1,8 @@
-// frame_args.hpp — what the streaming per-pixel units (dark.hip, flat.hip) share: the 64 x 4 tile of a
-// 256-thread workgroup, vectors of adjacent pixels, the argument checks of their entry points and the
-// dispatch on the element type.
+// frame_args.hpp — what the seven calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
+// ovs.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks, the
+// known element types and the dispatch on them, and the checks and grid of the 64 x 4 tiles.  Device side, for
+// the streaming per-pixel kernels of dark / flat / tss / ovs: a lane's pixel on that tile grid and vectors of
+// adjacent pixels.  launch.hpp makes the typed launch.
 #pragma once
 #include "common.hpp"
 
@@ -28,13 +30,23 @@ struct Span {
   const void* p;
   size_t bytes;
 };
-inline Span span2d(const void* p, int h, long w, long pitch, size_t es) {
-  return {p, p ? ((size_t)(h - 1) * pitch + w) * es : 0};
+// n frames of h rows of w elements, `stride` elements from one frame to the next; empty for a null pointer
+inline Span span_stack(const void* p, int n, int h, long w, long pitch, long stride, size_t es) {
+  return {p, p ? ((size_t)(n - 1) * stride + (size_t)(h - 1) * pitch + w) * es : 0};
 }
+inline Span span2d(const void* p, int h, long w, long pitch, size_t es) { return span_stack(p, 1, h, w, pitch, 0, es); }
 inline bool overlap(Span a, Span b) {
   if (!a.p || !b.p) return false;
   const char *pa = (const char*)a.p, *pb = (const char*)b.p;
   return pa < pb + b.bytes && pb < pa + a.bytes;
+}
+// does one of the first k spans - the arrays a call writes - overlap any other of the n?
+template <int N>
+bool written_overlaps(const Span (&s)[N], int k) {
+  for (int i = 0; i < k; i++)
+    for (int j = 0; j < N; j++)
+      if (j != i && overlap(s[i], s[j])) return true;
+  return false;
 }
 
 // f(T{}) for the element type of `dtype`; the caller has refused unknown dtypes

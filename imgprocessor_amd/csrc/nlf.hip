@@ -22,6 +22,8 @@
 //            frame mostly share a bin.  The waves' tables merge into one slab row per workgroup,
 //            written with plain stores (zeros where the workgroup got no pixel).
 #include "common.hpp"
+#include "frame_args.hpp"
+#include "launch.hpp"
 #include "nlf_fn.hpp"
 
 #pragma clang fp contract(off)
@@ -313,18 +315,6 @@ snr_map_kernel(SnrArgs a, int tiles_x) {
   a.out[(long)y * a.out_pitch + x] = snr;
 }
 
-bool known_dtype(int dtype) {
-  return dtype == IPA_U8 || dtype == IPA_U16 || dtype == IPA_F32 || dtype == IPA_F64;
-}
-
-// do [a, a + na) and [b, b + nb) share a byte (either may be NULL)?
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b) return false;
-  const char *pa = (const char*)a, *pb = (const char*)b;
-  return pa < pb + nb && pb < pa + na;
-}
-size_t span_bytes(int h, int w, long pitch, size_t es) { return ((size_t)(h - 1) * pitch + w) * es; }
-
 // the argument checks of the calls that read the frame(s) of an NlfSrc
 int check_src(ipa_ctx* ctx, const char* what, const void* d_img, int dtype, const void* d_img2, int h,
               int w, long pitch, long pitch2, const double* d_bg, long bg_pitch) {
@@ -338,49 +328,28 @@ int check_src(ipa_ctx* ctx, const char* what, const void* d_img, int dtype, cons
   return IPA_OK;
 }
 
-template <typename... Args>
-void launch_signal(int dtype, dim3 grid, hipStream_t st, Args... args) {
-  dim3 block(kNlfThreads);
-  switch (dtype) {
-    case IPA_U8: hipLaunchKernelGGL(nlf_signal_kernel<unsigned char>, grid, block, 0, st, args...); break;
-    case IPA_U16: hipLaunchKernelGGL(nlf_signal_kernel<unsigned short>, grid, block, 0, st, args...); break;
-    case IPA_F32: hipLaunchKernelGGL(nlf_signal_kernel<float>, grid, block, 0, st, args...); break;
-    default: hipLaunchKernelGGL(nlf_signal_kernel<double>, grid, block, 0, st, args...); break;
-  }
-}
-
-template <int PASS>
-void launch_moments(int dtype, dim3 grid, hipStream_t st, const void* img, int h, int w, long pitch,
-                    const double* res, Moments* part) {
-  dim3 block(kNlfThreads);
-  switch (dtype) {
-    case IPA_U8:
-      hipLaunchKernelGGL((nlf_moments_kernel<unsigned char, PASS>), grid, block, 0, st, (const unsigned char*)img, h,
-                         w, pitch, res, part);
-      break;
-    case IPA_U16:
-      hipLaunchKernelGGL((nlf_moments_kernel<unsigned short, PASS>), grid, block, 0, st, (const unsigned short*)img,
-                         h, w, pitch, res, part);
-      break;
-    case IPA_F32:
-      hipLaunchKernelGGL((nlf_moments_kernel<float, PASS>), grid, block, 0, st, (const float*)img, h, w, pitch, res,
-                         part);
-      break;
-    default:
-      hipLaunchKernelGGL((nlf_moments_kernel<double, PASS>), grid, block, 0, st, (const double*)img, h, w, pitch,
-                         res, part);
-      break;
-  }
-}
-
 int signal_call(ipa_ctx* ctx, const char* what, const NlfSrc& src, int dtype, int h, int w, double* d_out,
                 long out_pitch) {
-  const int tiles_x = (w + 63) / 64, tiles_y = (h + 3) / 4;
-  IPA_REQUIRE(ctx, (long)tiles_x * tiles_y <= 0x7fffffffL, "%s: image too large", what);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  launch_signal(dtype, dim3((unsigned)(tiles_x * tiles_y)), ctx->stream, src, h, w, tiles_x, d_out, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  int tiles_x;
+  unsigned grid;
+  const int rc = frame_args(ctx, what, h, w, &tiles_x, &grid);
+  if (rc) return rc;
+  return by_dtype(dtype, [&](auto e) {
+    return launch(ctx, nlf_signal_kernel<decltype(e)>, dim3(grid), dim3(kNlfThreads), 0, src, h, w, tiles_x, d_out,
+                  out_pitch);
+  });
+}
+
+// one pass of the moments: the partials of `grid` workgroups, then their sum into res
+template <int PASS>
+int moments_pass(ipa_ctx* ctx, int dtype, int grid, const void* d_img, int h, int w, long pitch, double* res,
+                 Moments* part) {
+  const int rc = by_dtype(dtype, [&](auto e) {
+    return launch(ctx, nlf_moments_kernel<decltype(e), PASS>, dim3(grid), dim3(kNlfThreads), 0, d_img, h, w, pitch,
+                  res, part);
+  });
+  if (rc) return rc;
+  return launch(ctx, nlf_moments_final<PASS>, dim3(1), dim3(kNlfThreads), 0, part, grid, (long)h * w, res);
 }
 
 // workgroups of a persistent launch: what the work needs, at most `per_cu` per compute unit
@@ -409,11 +378,10 @@ int ipa_nlf_signal_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d
   int rc = check_src(ctx, "nlf_signal", d_img, dtype, d_img2, h, w, pitch, pitch2, d_bg, bg_pitch);
   if (rc) return rc;
   IPA_REQUIRE(ctx, d_signal && signal_pitch >= w, "nlf_signal: null signal or pitch smaller than width");
-  const size_t es = ipa_dtype_size(dtype), out_bytes = span_bytes(h, w, signal_pitch, 8);
-  IPA_REQUIRE(ctx, !ranges_overlap(d_signal, out_bytes, d_img, span_bytes(h, w, pitch, es)) &&
-                       !ranges_overlap(d_signal, out_bytes, d_img2, span_bytes(h, w, pitch2, es)) &&
-                       !ranges_overlap(d_signal, out_bytes, d_bg, span_bytes(h, w, bg_pitch, 8)),
-              "nlf_signal does not run in place");
+  const size_t es = ipa_dtype_size(dtype);
+  const Span spans[] = {span2d(d_signal, h, w, signal_pitch, 8), span2d(d_img, h, w, pitch, es),
+                        span2d(d_img2, h, w, pitch2, es), span2d(d_bg, h, w, bg_pitch, 8)};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 1), "nlf_signal does not run in place");
   const NlfSrc src = {d_img, d_img2, d_bg, pitch, pitch2, bg_pitch, bg, 1};
   return signal_call(ctx, "nlf_signal", src, dtype, h, w, d_signal, signal_pitch);
 }
@@ -433,13 +401,10 @@ int ipa_nlf_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w
   if (rc) return rc;
   Moments* part = (Moments*)ctx->ws;
   double* res = (double*)((char*)ctx->ws + part_bytes);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  dim3 block(kNlfThreads);
-  launch_moments<0>(dtype, dim3(grid), ctx->stream, d_img, h, w, pitch, res, part);
-  hipLaunchKernelGGL(nlf_moments_final<0>, dim3(1), block, 0, ctx->stream, part, grid, (long)h * w, res);
-  launch_moments<1>(dtype, dim3(grid), ctx->stream, d_img, h, w, pitch, res, part);
-  hipLaunchKernelGGL(nlf_moments_final<1>, dim3(1), block, 0, ctx->stream, part, grid, (long)h * w, res);
-  IPA_HIP(ctx, hipGetLastError());
+  rc = moments_pass<0>(ctx, dtype, grid, d_img, h, w, pitch, res, part);
+  if (rc) return rc;
+  rc = moments_pass<1>(ctx, dtype, grid, d_img, h, w, pitch, res, part);
+  if (rc) return rc;
   IPA_HIP(ctx, hipMemcpyAsync(moments, res, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return IPA_OK;
@@ -472,6 +437,7 @@ int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_i
   rc = ipa_ws_reserve(ctx, o_slab_cnt + (size_t)grid * nbins * 4);
   if (rc) return rc;
   char* ws = (char*)ctx->ws;
+  void *d_cnt = ws + o_cnt, *d_sum = ws + o_sum;
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   IPA_HIP(ctx, hipMemcpyAsync(ws, edges, (size_t)(nbins + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   BinArgs a;
@@ -487,19 +453,15 @@ int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_i
   a.rms = rms;
   a.slab_cnt = (unsigned*)(ws + o_slab_cnt);
   a.slab_sum = (double*)(ws + o_slab_sum);
-  dim3 g(grid), block(waves * 64);
-  switch (dtype) {
-    case IPA_U8: hipLaunchKernelGGL(nlf_bins_kernel<unsigned char>, g, block, lds, ctx->stream, a); break;
-    case IPA_U16: hipLaunchKernelGGL(nlf_bins_kernel<unsigned short>, g, block, lds, ctx->stream, a); break;
-    case IPA_F32: hipLaunchKernelGGL(nlf_bins_kernel<float>, g, block, lds, ctx->stream, a); break;
-    default: hipLaunchKernelGGL(nlf_bins_kernel<double>, g, block, lds, ctx->stream, a); break;
-  }
-  hipLaunchKernelGGL(nlf_bins_final, dim3(nbins), dim3(kNlfThreads), 0,
-                     ctx->stream, a.slab_cnt, a.slab_sum, grid, nbins, (unsigned long long*)(ws + o_cnt),
-                     (double*)(ws + o_sum));
-  IPA_HIP(ctx, hipGetLastError());
-  IPA_HIP(ctx, hipMemcpyAsync(counts, ws + o_cnt, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(sums, ws + o_sum, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
+  rc = by_dtype(dtype, [&](auto e) {
+    return launch(ctx, nlf_bins_kernel<decltype(e)>, dim3(grid), dim3(waves * 64), lds, a);
+  });
+  if (rc) return rc;
+  rc = launch(ctx, nlf_bins_final, dim3(nbins), dim3(kNlfThreads), 0, a.slab_cnt, a.slab_sum, grid, nbins, d_cnt,
+              d_sum);
+  if (rc) return rc;
+  IPA_HIP(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
+  IPA_HIP(ctx, hipMemcpyAsync(sums, d_sum, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
   IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return IPA_OK;
 }
@@ -509,15 +471,15 @@ int ipa_snr_map_dev(ipa_ctx* ctx, const double* d_signal, int h, int w, long pit
                     double bg_level, double* d_snr, long snr_pitch) {
   if (!ctx) return IPA_ERR_BAD_ARG;
   IPA_REQUIRE(ctx, d_signal && d_snr, "snr_map: null pointer");
-  IPA_REQUIRE(ctx, h > 0 && w > 0, "snr_map: empty image");
+  int tiles_x;
+  unsigned grid;
+  const int rc = frame_args(ctx, "snr_map", h, w, &tiles_x, &grid);
+  if (rc) return rc;
   IPA_REQUIRE(ctx, pitch >= w && snr_pitch >= w && (!d_noise || noise_pitch >= w),
               "snr_map: pitch smaller than width");
   IPA_REQUIRE(ctx, !(nlf && d_noise), "snr_map: a triple or a noise array, not both");
-  IPA_REQUIRE(ctx, !ranges_overlap(d_snr, span_bytes(h, w, snr_pitch, 8), d_noise,
-                                   span_bytes(h, w, noise_pitch, 8)),
+  IPA_REQUIRE(ctx, !overlap(span2d(d_snr, h, w, snr_pitch, 8), span2d(d_noise, h, w, noise_pitch, 8)),
               "snr_map: the map overlaps the noise array");
-  const int tiles_x = (w + 63) / 64, tiles_y = (h + 3) / 4;
-  IPA_REQUIRE(ctx, (long)tiles_x * tiles_y <= 0x7fffffffL, "snr_map: image too large");
   SnrArgs a;
   a.signal = d_signal;
   a.signal_pitch = pitch;
@@ -534,11 +496,7 @@ int ipa_snr_map_dev(ipa_ctx* ctx, const double* d_signal, int h, int w, long pit
   a.bg_level = bg_level;
   a.out = d_snr;
   a.out_pitch = snr_pitch;
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(snr_map_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(kNlfThreads), 0, ctx->stream, a,
-                     tiles_x);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return launch(ctx, snr_map_kernel, dim3(grid), dim3(kNlfThreads), 0, a, tiles_x);
 }
 
 int ipa_snr_bg_median_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,

@@ -23,6 +23,7 @@
 // P[p] + sum w (P[p + t] - P[p]) / sum w with one division: the weighted mean, exact where every
 // surviving neighbour equals the pixel (a constant image, a cut-off only the self pair passes).
 #include "common.hpp"
+#include "frame_args.hpp"
 #include "launch.hpp"
 
 namespace ipa {
@@ -159,35 +160,19 @@ size_t nlm_lds_bytes(int s, int d) {
   return (size_t)(kNlmWaves * NlmRows<T>::R + s - 2 + 2 * d) * (64 + 2 * d) * sizeof(T);
 }
 
-template <typename T, int W>
-int nlm_launch(ipa_ctx* ctx, dim3 frames_grid, const NlmArgs& a) {
-  const size_t lds = nlm_lds_bytes<T>(W + 1, a.d);
-  dim3 grid((a.w + 64 - W) / (65 - W), (a.h + kNlmWaves * NlmRows<T>::R - 1) / (kNlmWaves * NlmRows<T>::R),
-            frames_grid.z);
-  hipLaunchKernelGGL((nlm_kernel<T, W>), grid, dim3(64 * kNlmWaves), lds, ctx->stream, a);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
-}
-
+// the kernel of the odd patch size s = 3 ... 11 (W = s - 1) over n frames; W listed last first: pick
+// instantiates, and the code object lays out, from the back
 template <typename T>
 int nlm_dispatch(ipa_ctx* ctx, int s, int n, const NlmArgs& a) {
-  IPA_REQUIRE(ctx, nlm_lds_bytes<T>(s, a.d) <= (size_t)kNlmLdsBytes,
-              "nl_means: the tile of patch_size %d, patch_distance %d needs %zu bytes of LDS (limit %d)", s, a.d,
-              nlm_lds_bytes<T>(s, a.d), kNlmLdsBytes);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  const dim3 fg(1, 1, n);
-  switch (s) {
-    case 3: return nlm_launch<T, 2>(ctx, fg, a);
-    case 5: return nlm_launch<T, 4>(ctx, fg, a);
-    case 7: return nlm_launch<T, 6>(ctx, fg, a);
-    case 9: return nlm_launch<T, 8>(ctx, fg, a);
-    default: return nlm_launch<T, 10>(ctx, fg, a);
-  }
-}
-
-bool spans_overlap(const void* p, size_t pb, const void* q, size_t qb) {
-  const char *a = (const char*)p, *b = (const char*)q;
-  return a < b + qb && b < a + pb;
+  const size_t lds = nlm_lds_bytes<T>(s, a.d);
+  IPA_REQUIRE(ctx, lds <= (size_t)kNlmLdsBytes,
+              "nl_means: the tile of patch_size %d, patch_distance %d needs %zu bytes of LDS (limit %d)", s, a.d, lds,
+              kNlmLdsBytes);
+  constexpr int TY = kNlmWaves * NlmRows<T>::R;
+  return pick<10, 8, 6, 4, 2>(s - 1, [&](auto W) {
+    return launch(ctx, nlm_kernel<T, W()>, dim3((a.w + 64 - W()) / (65 - W()), (a.h + TY - 1) / TY, n),
+                  dim3(64 * kNlmWaves), lds, a);
+  });
 }
 
 }  // namespace
@@ -201,20 +186,21 @@ int ipa_nl_means_dev(ipa_ctx* ctx, const void* d_src, int dtype, int n, int h, i
                      long frame_stride, int patch_size, int patch_distance, double h_cut, double sigma,
                      void* d_dst, long dst_pitch, long dst_frame_stride) {
   if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, d_src && d_dst, "null pointer");
+  IPA_REQUIRE(ctx, d_src && d_dst, "nl_means: null pointer");
   IPA_REQUIRE(ctx, n >= 1 && n <= 65535 && h >= 2 && w >= 2,
               "nl_means needs 1 ... 65535 frames of at least 2 x 2 pixels");
-  IPA_REQUIRE(ctx, pitch >= w && dst_pitch >= w, "pitch smaller than width");
-  const long frame = (long)(h - 1) * pitch + w, dframe = (long)(h - 1) * dst_pitch + w;
-  IPA_REQUIRE(ctx, n == 1 || (frame_stride >= frame && dst_frame_stride >= dframe), "frames overlap");
+  IPA_REQUIRE(ctx, pitch >= w && dst_pitch >= w, "nl_means: pitch smaller than width");
+  IPA_REQUIRE(ctx, n == 1 || (frame_stride >= (long)(h - 1) * pitch + w &&
+                              dst_frame_stride >= (long)(h - 1) * dst_pitch + w),
+              "nl_means: frames overlap");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "nl_means: frames are float32 / float64 (got dtype %d)", dtype);
   IPA_REQUIRE(ctx, patch_size >= 2 && patch_size <= 11, "nl_means: patch_size %d is not in 2 ... 11", patch_size);
   IPA_REQUIRE(ctx, patch_distance >= 0, "nl_means: patch_distance %d is negative", patch_distance);
   IPA_REQUIRE(ctx, h_cut > 0 && sigma >= 0, "nl_means: h must be positive and sigma not negative");
-  const size_t es = dtype == IPA_F32 ? 4 : 8;
-  IPA_REQUIRE(ctx, !spans_overlap(d_src, ((size_t)(n - 1) * frame_stride + frame) * es, d_dst,
-                                  ((size_t)(n - 1) * dst_frame_stride + dframe) * es),
+  const size_t es = ipa_dtype_size(dtype);
+  IPA_REQUIRE(ctx, !overlap(span_stack(d_src, n, h, w, pitch, frame_stride, es),
+                            span_stack(d_dst, n, h, w, dst_pitch, dst_frame_stride, es)),
               "nl_means does not run in place");
   const int s = patch_size | 1;   // an even size is the next odd one
   NlmArgs a;
@@ -229,15 +215,15 @@ int ipa_nl_means_dev(ipa_ctx* ctx, const void* d_src, int dtype, int n, int h, i
   a.d = patch_distance;
   a.inv = 1.0 / ((double)s * s * h_cut * h_cut);
   a.sig = 2.0 * sigma * sigma * (double)(s - 1) * (s - 1);
-  return dtype == IPA_F32 ? nlm_dispatch<float>(ctx, s, n, a) : nlm_dispatch<double>(ctx, s, n, a);
+  return by_float(dtype, [&](auto t) { return nlm_dispatch<decltype(t)>(ctx, s, n, a); });
 }
 
 int ipa_nan_to_zero_dev(ipa_ctx* ctx, void* d_img, int dtype, int n, int h, int w, long pitch,
                         long frame_stride) {
   if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, d_img, "null pointer");
+  IPA_REQUIRE(ctx, d_img, "nan_to_zero: null pointer");
   IPA_REQUIRE(ctx, n >= 1 && n <= 65535 && h > 0 && w > 0, "nan_to_zero needs 1 ... 65535 non-empty frames");
-  IPA_REQUIRE(ctx, pitch >= w, "pitch smaller than width");
+  IPA_REQUIRE(ctx, pitch >= w, "nan_to_zero: pitch smaller than width");
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "nan_to_zero: frames are float32 / float64 (got dtype %d)", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4, n), block(64, 4);

@@ -176,7 +176,7 @@ int ovs_common(ipa_ctx* ctx, const char* what, const void* d_fits, int dtype, in
   IPA_REQUIRE(ctx, fit_frame_stride >= (long)(oh - 1) * fit_pitch + ow, "%s: frames overlap", what);
   if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "%s: fitted images are uint8 / uint16 / float32 / float64 (got dtype %d)", what, dtype);
-  *fits = {d_fits, ((size_t)(n - 1) * fit_frame_stride + (size_t)(oh - 1) * fit_pitch + ow) * ipa_dtype_size(dtype)};
+  *fits = span_stack(d_fits, n, oh, ow, fit_pitch, fit_frame_stride, ipa_dtype_size(dtype));
   return IPA_OK;
 }
 
@@ -200,10 +200,8 @@ int ipa_ovs_object_dev(ipa_ctx* ctx, const double* d_ff, int fh, int fw, long ff
   // the sampler addresses the flat field with 32-bit byte offsets
   IPA_REQUIRE(ctx, (long)(fh - 1) * ff_pitch + fw < (1L << 28), "ovs_object: flat field too large");
   const Span ff = span2d(d_ff, fh, fw, ff_pitch, 8);
-  const Span out[2] = {span2d(d_obj, oh, ow, obj_pitch, 8), span2d(d_count, oh, ow, count_pitch, 4)};
-  IPA_REQUIRE(ctx, !overlap(out[0], out[1]), "ovs_object: the outputs overlap");
-  for (const Span& o : out)
-    IPA_REQUIRE(ctx, !overlap(o, ff) && !overlap(o, fits), "ovs_object: an output overlaps an input");
+  const Span spans[] = {span2d(d_obj, oh, ow, obj_pitch, 8), span2d(d_count, oh, ow, count_pitch, 4), ff, fits};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 2), "ovs_object: an output overlaps another array");
   int tiles_x;
   unsigned grid;
   rc = frame_args(ctx, "ovs_object", oh, ow, &tiles_x, &grid);
@@ -236,16 +234,13 @@ int ipa_ovs_flatfield_dev(ipa_ctx* ctx, const double* d_obj, long obj_pitch, con
   const int sh = d_sub && sub_step > 0 ? (fh + sub_step - 1) / sub_step : 0;
   const int sw = d_sub && sub_step > 0 ? (fw + sub_step - 1) / sub_step : 0;
   IPA_REQUIRE(ctx, !d_sub || (sub_step >= 1 && sub_pitch >= sw), "ovs_flatfield: bad every-n-th grid");
-  const Span masks = {d_masks, (size_t)(n - 1) * mask_frame_stride + (size_t)(oh - 1) * mask_pitch + ow};
-  const Span obj = span2d(d_obj, oh, ow, obj_pitch, 8);
-  const Span out[3] = {span2d(d_ff, fh, fw, ff_pitch, 8), span2d(d_count, fh, fw, count_pitch, 4),
-                       span2d(d_sub, sh, sw, sub_pitch, 8)};
-  for (int i = 0; i < 3; i++) {
-    for (int j = i + 1; j < 3; j++)
-      IPA_REQUIRE(ctx, !overlap(out[i], out[j]), "ovs_flatfield: the outputs overlap");
-    IPA_REQUIRE(ctx, !overlap(out[i], obj) && !overlap(out[i], fits) && !overlap(out[i], masks),
-                "ovs_flatfield: an output overlaps an input");
-  }
+  const Span spans[] = {span2d(d_ff, fh, fw, ff_pitch, 8),
+                        span2d(d_count, fh, fw, count_pitch, 4),
+                        span2d(d_sub, sh, sw, sub_pitch, 8),
+                        span2d(d_obj, oh, ow, obj_pitch, 8),
+                        fits,
+                        span_stack(d_masks, n, oh, ow, mask_pitch, mask_frame_stride, 1)};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 3), "ovs_flatfield: an output overlaps another array");
   int tiles_x;
   unsigned grid;
   rc = frame_args(ctx, "ovs_flatfield", fh, fw, &tiles_x, &grid);
@@ -274,11 +269,9 @@ int ipa_masked_running_mean_dev(ipa_ctx* ctx, double* d_avg, long avg_pitch, int
               "masked_running_mean: pitch smaller than width");
   if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "masked_running_mean: data is uint8 / uint16 / float32 / float64 (got dtype %d)", dtype);
-  const Span avg = span2d(d_avg, h, w, avg_pitch, 8), cnt = span2d(d_n, h, w, n_pitch, 4);
-  const Span data = span2d(d_data, h, w, data_pitch, ipa_dtype_size(dtype)), mask = span2d(d_mask, h, w, mask_pitch, 1);
-  IPA_REQUIRE(ctx, !overlap(avg, cnt), "masked_running_mean: average and count overlap");
-  for (const Span& o : {avg, cnt})
-    IPA_REQUIRE(ctx, !overlap(o, data) && !overlap(o, mask), "masked_running_mean: the state overlaps an input");
+  const Span spans[] = {span2d(d_avg, h, w, avg_pitch, 8), span2d(d_n, h, w, n_pitch, 4),
+                        span2d(d_data, h, w, data_pitch, ipa_dtype_size(dtype)), span2d(d_mask, h, w, mask_pitch, 1)};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 2), "masked_running_mean: the state overlaps another array");
   return by_dtype(dtype, [&](auto e) {
     using E = decltype(e);
     return launch(ctx, masked_running_mean_kernel<E>, dim3(grid), dim3(kOvsThreads), 0, d_avg, avg_pitch, d_n, n_pitch,

@@ -19,6 +19,8 @@
 // rounded: results equal numpy's bits.  FP contraction is off for this file (Makefile + pragma)
 // because numpy never fuses and a fused `x - a * sqrt(..)` would not round like it.
 #include "common.hpp"
+#include "frame_args.hpp"
+#include "launch.hpp"
 #include "nlf_fn.hpp"
 
 #pragma clang fp contract(off)
@@ -218,32 +220,6 @@ remove_single_pixels_kernel(const unsigned char* __restrict__ in, int h, int w, 
   out[(long)y * out_pitch + x] = v;
 }
 
-size_t elem_size(int dtype) { return dtype == IPA_U8 ? 1 : dtype == IPA_U16 ? 2 : dtype == IPA_F32 ? 4 : 8; }
-
-struct Span {
-  const void* p;
-  size_t bytes;
-};
-Span span2d(const void* p, int h, int w, long pitch, size_t es) {
-  return {p, p ? ((size_t)(h - 1) * pitch + w) * es : 0};
-}
-bool overlap(Span a, Span b) {
-  if (!a.p || !b.p) return false;
-  const char *pa = (const char*)a.p, *pb = (const char*)b.p;
-  return pa < pb + b.bytes && pb < pa + a.bytes;
-}
-
-template <int F>
-void ste_launch_f(int dtype, dim3 grid, hipStream_t st, const SteArgs& a) {
-  dim3 block(64 * kSteWaves);
-  switch (dtype) {
-    case IPA_U8: hipLaunchKernelGGL((ste_kernel<unsigned char, F>), grid, block, 0, st, a); break;
-    case IPA_U16: hipLaunchKernelGGL((ste_kernel<unsigned short, F>), grid, block, 0, st, a); break;
-    case IPA_F32: hipLaunchKernelGGL((ste_kernel<float, F>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((ste_kernel<double, F>), grid, block, 0, st, a); break;
-  }
-}
-
 }  // namespace
 }  // namespace ipa
 
@@ -256,27 +232,26 @@ int ipa_ste_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int
                 int* d_count, double* d_thr, long state_pitch, const unsigned char* d_mask,
                 unsigned char* d_mask_ste, unsigned char* d_mask_clean, long mask_pitch) {
   if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, d_frames && d_avg && d_count, "null pointer");
-  IPA_REQUIRE(ctx, d_thr, "d_thr is NULL: the threshold is always kept in the state");
-  IPA_REQUIRE(ctx, h > 0 && w > 0, "empty image");
-  IPA_REQUIRE(ctx, first_pair ? n >= 2 : n >= 1, "the first pair needs n >= 2 frames (got %d)", n);
-  IPA_REQUIRE(ctx, pitch >= w && state_pitch >= w, "pitch smaller than width");
+  IPA_REQUIRE(ctx, d_frames && d_avg && d_count, "ste: null pointer");
+  IPA_REQUIRE(ctx, d_thr, "ste: d_thr is NULL: the threshold is always kept in the state");
+  IPA_REQUIRE(ctx, h > 0 && w > 0, "ste: empty image");
+  IPA_REQUIRE(ctx, first_pair ? n >= 2 : n >= 1, "ste: the first pair needs n >= 2 frames (got %d)", n);
+  IPA_REQUIRE(ctx, pitch >= w && state_pitch >= w, "ste: pitch smaller than width");
   IPA_REQUIRE(ctx, !(d_mask || d_mask_ste || d_mask_clean) || mask_pitch >= w,
-              "mask pitch smaller than width");
-  IPA_REQUIRE(ctx, n == 1 || frame_stride >= (long)(h - 1) * pitch + w, "frames overlap");
-  if (dtype != IPA_U8 && dtype != IPA_U16 && dtype != IPA_F32 && dtype != IPA_F64)
+              "ste: mask pitch smaller than width");
+  IPA_REQUIRE(ctx, n == 1 || frame_stride >= (long)(h - 1) * pitch + w, "ste: frames overlap");
+  if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "ste: frames are uint8 / uint16 / float32 / float64 (got dtype %d)", dtype);
-  const size_t es = elem_size(dtype);
-  const Span fr = {d_frames, ((size_t)(n - 1) * frame_stride + (size_t)(h - 1) * pitch + w) * es};
-  const Span avg = span2d(d_avg, h, w, state_pitch, 8), cnt = span2d(d_count, h, w, state_pitch, 4),
-             thr = span2d(d_thr, h, w, state_pitch, 8), msk = span2d(d_mask, h, w, mask_pitch, 1),
-             mste = span2d(d_mask_ste, h, w, mask_pitch, 1),
-             mcl = span2d(d_mask_clean, h, w, mask_pitch, 1);
+  const size_t es = ipa_dtype_size(dtype);
   // the first five are written; none may overlap another array of the call
-  const Span spans[] = {avg, cnt, thr, mste, mcl, fr, msk};
-  for (int i = 0; i < 5; i++)
-    for (int j = 0; j < 7; j++)
-      if (j != i) IPA_REQUIRE(ctx, !overlap(spans[i], spans[j]), "state, masks and frames overlap");
+  const Span spans[] = {span2d(d_avg, h, w, state_pitch, 8),
+                        span2d(d_count, h, w, state_pitch, 4),
+                        span2d(d_thr, h, w, state_pitch, 8),
+                        span2d(d_mask_ste, h, w, mask_pitch, 1),
+                        span2d(d_mask_clean, h, w, mask_pitch, 1),
+                        span_stack(d_frames, n, h, w, pitch, frame_stride, es),
+                        span2d(d_mask, h, w, mask_pitch, 1)};
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 5), "ste: state, masks and frames overlap");
 
   const int steps = first_pair ? n - 1 : n;
   const int fmax = ctx->tune.ste_frames <= 1 ? 1 : kSteMaxF;
@@ -334,11 +309,13 @@ int ipa_ste_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int
     a.mask_clean = l == launches - 1 ? d_mask_clean : nullptr;
     a.mask_pitch = mask_pitch;
     dim3 grid((w + kSteW - 2 * st - 1) / (kSteW - 2 * st), (h + kSteH - 2 * st - 1) / (kSteH - 2 * st));
-    if (fmax == 1)
-      ste_launch_f<1>(dtype, grid, ctx->stream, a);
-    else
-      ste_launch_f<kSteMaxF>(dtype, grid, ctx->stream, a);
-    IPA_HIP(ctx, hipGetLastError());
+    // (listed last first: pick instantiates, and the code object lays out, from the back)
+    const int rc = pick<kSteMaxF, 1>(fmax, [&](auto F) {
+      return by_dtype(dtype, [&](auto e) {
+        return launch(ctx, ste_kernel<decltype(e), F()>, grid, dim3(64 * kSteWaves), 0, a);
+      });
+    });
+    if (rc) return rc;
     in_avg = a.avg_out;
     in_cnt = a.count_out;
     in_pitch = a.out_pitch;
@@ -350,17 +327,13 @@ int ipa_ste_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int
 int ipa_remove_single_pixels_dev(ipa_ctx* ctx, const unsigned char* d_in, int h, int w, long pitch,
                                  unsigned char* d_out, long out_pitch) {
   if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, d_in && d_out, "null pointer");
-  IPA_REQUIRE(ctx, h > 0 && w > 0, "empty image");
-  IPA_REQUIRE(ctx, pitch >= w && out_pitch >= w, "pitch smaller than width");
+  IPA_REQUIRE(ctx, d_in && d_out, "remove_single_pixels: null pointer");
+  IPA_REQUIRE(ctx, h > 0 && w > 0, "remove_single_pixels: empty image");
+  IPA_REQUIRE(ctx, pitch >= w && out_pitch >= w, "remove_single_pixels: pitch smaller than width");
   IPA_REQUIRE(ctx, !overlap(span2d(d_in, h, w, pitch, 1), span2d(d_out, h, w, out_pitch, 1)),
-              "removeSinglePixels does not run in place");
-  dim3 grid((w + 63) / 64, (h + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(remove_single_pixels_kernel, grid, block, 0, ctx->stream, d_in, h, w, pitch,
-                     d_out, out_pitch);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+              "remove_single_pixels does not run in place");
+  return launch(ctx, remove_single_pixels_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, d_in, h, w,
+                pitch, d_out, out_pitch);
 }
 
 }  // extern "C"

@@ -321,15 +321,15 @@ int ipa_tss_event_length_dev(ipa_ctx* ctx, const void* d_stack, int dtype, int T
               "tss_event_length: event frames overlap");
   if (!known_dtype(dtype))
     IPA_UNSUPPORTED(ctx, "tss_event_length: frames are uint8 / uint16 / float32 / float64 (got dtype %d)", dtype);
-  const Span st = {d_stack, ((size_t)(T - 1) * frame_stride + (size_t)(h - 1) * pitch + w) * ipa_dtype_size(dtype)};
-  const Span ev = {d_events, d_events ? (size_t)(T - 1) * ev_frame_stride + (size_t)(h - 1) * ev_pitch + w : 0};
   // outputs first: no output may touch another output or an input
-  const Span spans[] = {span2d(d_avlen, h, w, avlen_pitch, 8), span2d(d_zero_mask, h, w, mask_pitch, 1), ev, st,
-                        span2d(d_offset, h, w, plane_pitch, 8), span2d(d_ascent, h, w, plane_pitch, 8),
+  const Span spans[] = {span2d(d_avlen, h, w, avlen_pitch, 8),
+                        span2d(d_zero_mask, h, w, mask_pitch, 1),
+                        span_stack(d_events, T, h, w, ev_pitch, ev_frame_stride, 1),
+                        span_stack(d_stack, T, h, w, pitch, frame_stride, ipa_dtype_size(dtype)),
+                        span2d(d_offset, h, w, plane_pitch, 8),
+                        span2d(d_ascent, h, w, plane_pitch, 8),
                         span2d(d_error, h, w, plane_pitch, 8)};
-  for (int i = 0; i < 3; i++)
-    for (int j = i + 1; j < 7; j++)
-      IPA_REQUIRE(ctx, !overlap(spans[i], spans[j]), "tss_event_length: an output overlaps another array");
+  IPA_REQUIRE(ctx, !written_overlaps(spans, 3), "tss_event_length: an output overlaps another array");
   TssTimes t;
   for (int k = 0; k < kTssMaxT; k++) t.x[k] = k < T ? times[k] : 0.0;
   TssArgs a;

@@ -17,6 +17,7 @@ import numbers
 import numpy as np
 
 from .. import ops
+from .._staging import frame_stack
 from ..device import DeviceArray, default_context
 
 
@@ -87,14 +88,8 @@ class SingleTimeEffectDetection(object):
                 _check_frame(f if hasattr(f, 'shape') else np.asarray(f))
         if (frames.shape[0] if isinstance(frames, DeviceArray) else len(frames)) < 2:
             raise ValueError('SingleTimeEffectDetection needs at least 2 images')
-        self._dev = isinstance(frames, DeviceArray) or isinstance(frames[0], DeviceArray)
-        if isinstance(frames, list):
-            if self._dev:
-                if not all(isinstance(f, DeviceArray) for f in frames):
-                    raise TypeError('mix of host and device frames')
-                frames = self._stack_dev(frames)
-            else:
-                frames = np.stack([np.asarray(f) for f in frames])
+        frames = frame_stack('SingleTimeEffectDetection', frames)
+        self._dev = isinstance(frames, DeviceArray)
         self.save_ste_indices = save_ste_indices
         self.noise_level_function = noise_level_function
         self._ctx = frames.ctx if self._dev else default_context()
@@ -129,18 +124,6 @@ class SingleTimeEffectDetection(object):
             self._thr.set(np.broadcast_to(thr, (h, w)))
         ops.ste_update(frames, self._avg, self._count, self._thr, first_pair=True, nlf=triple,
                        nstd=nStd, mask_ste=self._ste, mask_clean=self._clean, ctx=ctx)
-
-    @staticmethod
-    def _stack_dev(frames):
-        f0 = frames[0]
-        for f in frames:
-            _check_frame(f)
-            if f.shape != f0.shape or f.dtype != f0.dtype or f.ctx is not f0.ctx:
-                raise ValueError('device frames must share shape, dtype and context')
-        st = DeviceArray(f0.ctx, (len(frames),) + f0.shape, f0.dtype)
-        for i, f in enumerate(frames):
-            st.frame(i).copy_from(f)
-        return st
 
     def _out(self, d, as_bool=False):
         if self._dev:

@@ -7,7 +7,8 @@ passes are kernels too.  Host frames give a host map, DeviceArrays a DeviceArray
 """
 import numpy as np
 
-from ... import ops, ops_nlf
+from ... import ops
+from ..._staging import _frame_pair
 from ...camera import NoiseLevelFunction as NLF
 from ...device import DeviceArray
 
@@ -29,7 +30,7 @@ def SNR(img1, img2=None, bg=None, noise_level_function=None, constant_noise_leve
     """
     if img2 is not None and bg is None:
         raise TypeError('SNR: a second image needs bg (the reference subtracts it from img2)')
-    dev, ctx, d1, d2, _, _ = ops_nlf._nlf_frames('SNR', img1, img2, None, (bg,))
+    dev, ctx, d1, d2, _, _ = _frame_pair('SNR', img1, img2, None, (bg,))
     if bg is not None and not isinstance(bg, DeviceArray) and np.ndim(bg) != 0:
         bg = ctx.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(bg, np.float64), d1.shape)))
     signal = ops.nlf_signal(d1, d2, bg=bg)

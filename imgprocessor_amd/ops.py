@@ -10,7 +10,8 @@ import numpy as np
 
 from . import _lib as L
 from .device import DeviceArray, default_context, dtype_id, as_frames
-from ._staging import _is_dev, _ctx_of, _p, _dptr, _dev_out, _stage_in, _stage_out  # noqa: F401
+from ._staging import (PIXEL_DTYPES, _is_dev, _ctx_of, _p, _dptr, _dev_out, _px_host, _stage_in,  # noqa: F401
+                       _stage_out)
 # the noise-level-function / SNR family lives in ops_nlf.py
 from .ops_nlf import nlf_signal, nlf_moments, nlf_bins, snr_map, snr_bg_median  # noqa: F401
 # the dark-current family lives in ops_dark.py
@@ -560,7 +561,7 @@ def calib_prefilter(img, bg=None, ff=None, threshold=0.1, out=None, ctx=None):
 
 
 # ------------------------------------------------- single-time effects --
-STE_DTYPES = (np.uint8, np.uint16, np.float32, np.float64)
+STE_DTYPES = PIXEL_DTYPES
 
 
 def _ste_state(a, shape, dtype, name):
@@ -588,10 +589,7 @@ def ste_update(frames, avg, count, thr, first_pair=False, nlf=None, nstd=4, mask
         if d.dtype not in STE_DTYPES:
             raise TypeError('ste_update: device frames must be uint8/uint16/float32/float64')
     else:
-        f = np.asarray(frames)
-        if f.dtype not in STE_DTYPES:
-            f = f.astype(np.float64)
-        d = ctx.to_device(np.ascontiguousarray(f))
+        d = ctx.to_device(_px_host(frames))
     n, h, w = as_frames(d)
     shape = (h, w)
     _ste_state(avg, shape, np.float64, 'avg')

@@ -7,14 +7,10 @@ import numpy as np
 
 from . import _lib as L
 from .device import DeviceArray, dtype_id
-from ._staging import _dev_out, _dptr, _is_dev, _stage_in, _stage_out
-from .ops_nlf import NLF_DTYPES, _f64_frame, _nlf_frames, _nlf_host
+from ._staging import (PIXEL_DTYPES, _dev_out, _dptr, _f64_frame, _f64_host, _frame_pair, _px_host, _stage_in,
+                       _stage_out, frame_stack)
 
 MAX_FRAMES = 64   # kDarkMaxT of csrc/dark.hip
-
-
-def _f64_host(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
 
 
 def pair_min(img, img2, ctx=None):
@@ -22,7 +18,7 @@ def pair_min(img, img2, ctx=None):
     oneImageNLF (features/SingleTimeEffectDetection.py:39-42; ipa_pair_min_dev).  uint8 / uint16 /
     float32 / float64 frames of one type (two host frames of different types both go to
     float64)."""
-    dev, ctx, d, d2, h, w = _nlf_frames('pair_min', img, img2, ctx)
+    dev, ctx, d, d2, h, w = _frame_pair('pair_min', img, img2, ctx)
     d_out = DeviceArray(ctx, (h, w), np.float64)
     ctx._check(ctx._lib.ipa_pair_min_dev(ctx.handle, d.ptr, d2.ptr, dtype_id(d.dtype), h, w, w, w,
                                          d_out.ptr, w), 'pair_min')
@@ -57,27 +53,6 @@ def nlf_threshold(x, nlf, nstd=1.0, out=None, ctx=None):
     return _stage_out(dev, d_out)
 
 
-def _stack(name, imgs, ctx):
-    """a (T, h, w) array or a list of T frames -> (dev, ctx, device stack)"""
-    if _is_dev(imgs):
-        frames = imgs
-    elif isinstance(imgs, np.ndarray):
-        frames = imgs
-    else:
-        frames = list(imgs)
-        if frames and all(_is_dev(f) for f in frames):
-            from .features.SingleTimeEffectDetection import SingleTimeEffectDetection
-            frames = SingleTimeEffectDetection._stack_dev(frames)
-        elif any(_is_dev(f) for f in frames):
-            raise TypeError('%s: mix of host and device frames' % name)
-        else:
-            frames = np.stack([np.asarray(f) for f in frames]) if frames else np.empty((0, 0, 0))
-    if len(frames.shape) != 3:
-        raise ValueError('%s takes a (T, h, w) stack or a list of (h, w) frames (got shape %s)'
-                         % (name, tuple(frames.shape)))
-    return frames
-
-
 def stack_linregress(times, imgs, mx_intensity=65535, min_ascent=0.001, ctx=None):
     """getLinearityFunction of camera/DarkCurrentMap.py:61-80 in one launch -> (offset, ascent,
     error), float64 (h, w): per pixel the line image(t) = offset + ascent * t through the frames
@@ -85,7 +60,7 @@ def stack_linregress(times, imgs, mx_intensity=65535, min_ascent=0.001, ctx=None
     (ipa_stack_linregress_dev, where the arithmetic is spelled out).  imgs: a (T, h, w) array or a
     list of T frames, uint8 / uint16 / float32 / float64, 2 <= T <= 64 (ValueError below,
     NotImplementedError above)."""
-    frames = _stack('stack_linregress', imgs, ctx)
+    frames = frame_stack('stack_linregress', imgs)
     t = np.ascontiguousarray(np.asarray(times, dtype=np.float64).ravel())
     n = frames.shape[0]
     if t.size != n:
@@ -94,7 +69,7 @@ def stack_linregress(times, imgs, mx_intensity=65535, min_ascent=0.001, ctx=None
         raise ValueError('stack_linregress: a line needs at least 2 frames (got %d)' % n)
     if n > MAX_FRAMES:
         raise NotImplementedError('stack_linregress: at most %d frames (got %d)' % (MAX_FRAMES, n))
-    dev, ctx, d, h, w = _stage_in('stack_linregress', frames, ctx, NLF_DTYPES, _nlf_host, ndims=(3,))
+    dev, ctx, d, h, w = _stage_in('stack_linregress', frames, ctx, PIXEL_DTYPES, _px_host, ndims=(3,))
     outs = [DeviceArray(ctx, (h, w), np.float64) for _ in range(3)]
     ctx._check(ctx._lib.ipa_stack_linregress_dev(
         ctx.handle, d.ptr, dtype_id(d.dtype), n, h, w, w, h * w, _dptr(t), float(mx_intensity),

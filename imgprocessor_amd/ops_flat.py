@@ -10,44 +10,11 @@ import numpy as np
 
 from . import _lib as L
 from .device import DeviceArray, dtype_id
-from ._staging import _dev_out, _is_dev, _stage_in, _stage_out
-from .ops_dark import _f64_host, nlf_params
-from .ops_nlf import NLF_DTYPES, _f64_frame, _nlf_host
+from ._staging import (PIXEL_DTYPES, _bg, _dev_out, _f64_frame, _f64_host, _is_dev, _px_host, _stage_in,
+                       _stage_out, frame_stack)
+from .ops_dark import nlf_params
 
 LUMA_WEIGHTS = (0.299, 0.587, 0.114)   # red, green, blue (transformations.py:132-134)
-
-
-def _bg(name, bg, shape, ctx):
-    """`img - bg` -> (device float64 frame or None, its pointer, pitch, scalar).  The frame is
-    returned so that it lives until the launch: a block that went back to the context's pool
-    would be handed out again as the result."""
-    if bg is None:
-        return None, None, 0, 0.0
-    if not _is_dev(bg) and np.ndim(bg) == 0:
-        return None, None, 0, float(bg)
-    if not _is_dev(bg):
-        bg = np.broadcast_to(np.asarray(bg, dtype=np.float64), shape)
-    d = _f64_frame(name, 'bg', bg, shape, ctx)
-    return d, d.ptr, shape[1], 0.0
-
-
-def check_dev_frames(name, frames):
-    """a non-empty list of DeviceArrays must share shape, dtype and context; nothing is allocated"""
-    f0 = frames[0]
-    for f in frames:
-        if f.shape != f0.shape or f.dtype != f0.dtype or f.ctx is not f0.ctx:
-            raise ValueError('%s: device frames must share shape, dtype and context' % name)
-
-
-def gather_dev(name, frames):
-    """a list of DeviceArrays (grey or colour) -> one (n, ...) DeviceArray, copied on the device"""
-    check_dev_frames(name, frames)
-    f0 = frames[0]
-    st = DeviceArray(f0.ctx, (len(frames),) + f0.shape, f0.dtype)
-    for k, f in enumerate(frames):
-        DeviceArray._wrap(st.ctx, C.c_void_p(st.ptr.value + k * f0.nbytes), f0.shape, f0.dtype, False,
-                          base=st).copy_from(f)
-    return st
 
 
 def stack_mean(imgs, ctx=None):
@@ -55,18 +22,7 @@ def stack_mean(imgs, ctx=None):
     divided by n: numpy's `out = float(f0); out += f; out /= n` bit for bit
     (transform/imgAverage.py:14-21; ipa_stack_mean_dev).  uint8 / uint16 / float32 / float64, any
     n >= 1.  Colour frames - a (n, h, w, 3) stack or a list of (h, w, 3) frames - give (h, w, 3)."""
-    frames = imgs
-    if not _is_dev(frames) and not isinstance(frames, np.ndarray):
-        frames = list(frames)
-        dev = [_is_dev(f) for f in frames]
-        if any(dev) and not all(dev):
-            raise TypeError('stack_mean: mix of host and device frames')
-        if not frames:
-            raise ValueError('stack_mean: no frames')
-        frames = gather_dev('stack_mean', frames) if dev[0] else np.stack([np.asarray(f) for f in frames])
-    if len(frames.shape) not in (3, 4):
-        raise ValueError('stack_mean takes a stack or a list of (h, w) or (h, w, 3) frames (got shape %s)'
-                         % (tuple(frames.shape),))
+    frames = frame_stack('stack_mean', imgs, ndims=(2, 3))
     if frames.shape[0] < 1:
         raise ValueError('stack_mean: no frames')
     if len(frames.shape) == 4:   # served as (n, h, w * c)
@@ -75,9 +31,9 @@ def stack_mean(imgs, ctx=None):
             flat = DeviceArray._wrap(frames.ctx, frames.ptr, (n, h, w * c), frames.dtype, False, base=frames)
             out = stack_mean(flat, ctx)
             return DeviceArray._wrap(out.ctx, out.ptr, (h, w, c), out.dtype, False, base=out)
-        return stack_mean(_nlf_host(frames).reshape(n, h, w * c), ctx).reshape(h, w, c)
+        return stack_mean(_px_host(frames).reshape(n, h, w * c), ctx).reshape(h, w, c)
     n = frames.shape[0]
-    dev, ctx, d, h, w = _stage_in('stack_mean', frames, ctx, NLF_DTYPES, _nlf_host, ndims=(3,))
+    dev, ctx, d, h, w = _stage_in('stack_mean', frames, ctx, PIXEL_DTYPES, _px_host, ndims=(3,))
     d_out = DeviceArray(ctx, (h, w), np.float64)
     ctx._check(ctx._lib.ipa_stack_mean_dev(ctx.handle, d.ptr, dtype_id(d.dtype), n, h, w, w, h * w,
                                            d_out.ptr, w), 'stack_mean')
@@ -123,7 +79,7 @@ def strided_median_max(img, step=10, ctx=None):
 def strided_min(img, step_y, step_x, ctx=None):
     """img[::step_y, ::step_x].min() in the frame's own type - a numpy scalar of uint8 / uint16 /
     float32 / float64 (camera/flatField/flatFieldFromCloseDistance.py:62; ipa_strided_extremum_dev)"""
-    dt, v = _extremum('strided_min', img, step_y, step_x, L.EXTREMUM_MIN, NLF_DTYPES, _nlf_host, ctx)
+    dt, v = _extremum('strided_min', img, step_y, step_x, L.EXTREMUM_MIN, PIXEL_DTYPES, _px_host, ctx)
     return dt.type(v)
 
 
@@ -149,7 +105,7 @@ def nlf_lower_mask(img, avg, nlf, nstd=6, out=None, ctx=None):
     kp = nlf_params(nlf)
     if kp is None:
         raise TypeError('nlf_lower_mask: the function carries no .triple, .poly or .constant')
-    dev, ctx, d, h, w = _stage_in('nlf_lower_mask', img, ctx, NLF_DTYPES, _nlf_host, (avg, out))
+    dev, ctx, d, h, w = _stage_in('nlf_lower_mask', img, ctx, PIXEL_DTYPES, _px_host, (avg, out))
     d_avg = _f64_frame('nlf_lower_mask', 'avg', avg, (h, w), ctx)
     d_out = _dev_out(ctx, out, (h, w), np.uint8) if dev else DeviceArray(ctx, (h, w), np.uint8)
     ctx._check(ctx._lib.ipa_nlf_lower_mask_dev(ctx.handle, d.ptr, dtype_id(d.dtype), h, w, w, d_avg.ptr, w,
@@ -175,7 +131,7 @@ def sens_shrink(img, bg=None, f=10, out=None, ctx=None):
     if len(shape) != 2:
         raise ValueError('sens_shrink works on 2-D arrays (got shape %s)' % (shape,))
     dh, dw = small_shape(shape, f)
-    dev, ctx, d, h, w = _stage_in('sens_shrink', img, ctx, NLF_DTYPES, _nlf_host, (bg, out))
+    dev, ctx, d, h, w = _stage_in('sens_shrink', img, ctx, PIXEL_DTYPES, _px_host, (bg, out))
     d_bg, bgp, bg_pitch, bgv = _bg('sens_shrink', bg, (h, w), ctx)
     d_out = _dev_out(ctx, out, (dh, dw), np.float64) if dev else DeviceArray(ctx, (dh, dw), np.float64)
     ctx._check(ctx._lib.ipa_sens_shrink_dev(ctx.handle, d.ptr, dtype_id(d.dtype), h, w, w, bgp, bg_pitch,
@@ -188,7 +144,7 @@ def sens_accumulate(img, small, acc, bg=None, first=False, n_last=0, ctx=None):
     n_last > 0; up = cv2.resize(small, img.shape, INTER_LINEAR), evaluated per pixel
     (camera/flatField/sensitivity.py:23-29; ipa_sens_accumulate_dev).  acc is a float64 (h, w)
     DeviceArray, updated in place and returned."""
-    dev, ctx, d, h, w = _stage_in('sens_accumulate', img, ctx, NLF_DTYPES, _nlf_host, (bg, small, acc))
+    dev, ctx, d, h, w = _stage_in('sens_accumulate', img, ctx, PIXEL_DTYPES, _px_host, (bg, small, acc))
     if not _is_dev(acc) or tuple(acc.shape) != (h, w) or acc.dtype != np.float64:
         raise ValueError('sens_accumulate: acc must be a float64 DeviceArray of shape %s' % ((h, w),))
     d_small = small if _is_dev(small) else ctx.to_device(_f64_host(small))

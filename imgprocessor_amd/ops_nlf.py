@@ -7,55 +7,10 @@ import numpy as np
 
 from . import _lib as L
 from .device import DeviceArray, dtype_id
-from ._staging import _ctx_of, _dev_out, _dptr, _is_dev, _p, _stage_in, _stage_out
+from ._staging import (PIXEL_DTYPES, _bg, _dev_out, _dptr, _f64_frame, _f64_host, _frame_pair, _p, _px_host,
+                       _stage_in, _stage_out)
 
-NLF_DTYPES = (np.uint8, np.uint16, np.float32, np.float64)
-
-
-def _nlf_host(a):
-    """host frames: uint8 / uint16 / float32 / float64 as they are, anything else as float64
-    (np.asfarray)"""
-    a = np.asarray(a)
-    return np.ascontiguousarray(a if a.dtype in NLF_DTYPES else a.astype(np.float64))
-
-
-def _nlf_frames(name, img, img2, ctx=None, others=()):
-    """The frame(s) of a call on the device -> (dev, ctx, d_img, d_img2 or None, h, w); dev: the
-    first frame came as a DeviceArray.  The kernels read a pair in ONE element type.  The
-    reference takes np.asfarray of each frame on its own, so two host frames of different types
-    both go up as float64 - never one cast to the other's type; where a DeviceArray is involved
-    nothing is converted, and a pair of different types is a ValueError."""
-    if img2 is not None and not _is_dev(img) and not _is_dev(img2):
-        img, img2 = _nlf_host(img), _nlf_host(img2)
-        if img.dtype != img2.dtype:
-            img, img2 = img.astype(np.float64), img2.astype(np.float64)
-    dev, ctx, d, h, w = _stage_in(name, img, ctx, NLF_DTYPES, _nlf_host, (img2,) + tuple(others))
-    d2 = None
-    if img2 is not None:
-        d2 = img2 if _is_dev(img2) else ctx.to_device(_nlf_host(img2))
-        if d2.dtype != d.dtype or tuple(d2.shape) != tuple(d.shape):
-            raise ValueError('%s: img2 (%s %s) must match the image\'s shape and dtype (%s %s)'
-                             % (name, d2.dtype, tuple(d2.shape), d.dtype, tuple(d.shape)))
-    return dev, ctx, d, d2, h, w
-
-
-def _f64_frame(name, what, a, shape, ctx):
-    """a float64 (h, w) side array (signal, noise) on the device"""
-    d = a if _is_dev(a) else ctx.to_device(np.ascontiguousarray(a, dtype=np.float64))
-    if d.dtype != np.float64 or tuple(d.shape) != tuple(shape):
-        raise ValueError('%s: %s must be a float64 array of shape %s' % (name, what, tuple(shape)))
-    return d
-
-
-def _nlf_bg(name, bg, shape, ctx):
-    """`img - bg` of measure/SNR/SNR.py:33-40 -> (device float64 array or None, pitch, scalar)"""
-    if bg is None:
-        return None, 0, 0.0
-    if not _is_dev(bg) and np.ndim(bg) == 0:
-        return None, 0, float(bg)
-    if not _is_dev(bg):
-        bg = np.broadcast_to(np.asarray(bg, dtype=np.float64), shape)
-    return _f64_frame(name, 'bg', bg, shape, ctx).ptr, shape[1], 0.0
+_nlf_frames = _frame_pair   # the name it had while it lived here
 
 
 def nlf_signal(img, img2=None, bg=None, ctx=None):
@@ -64,8 +19,8 @@ def nlf_signal(img, img2=None, bg=None, ctx=None):
     `frame - bg` (scalar or (h, w) array; None: as it is).  uint8 / uint16 / float32 / float64
     frames (other host types go to float64); host in, host out, DeviceArray in, DeviceArray out
     (ipa_nlf_signal_dev)."""
-    dev, ctx, d, d2, h, w = _nlf_frames('nlf_signal', img, img2, ctx, (bg,))
-    bgp, bg_pitch, bgv = _nlf_bg('nlf_signal', bg, (h, w), ctx)
+    dev, ctx, d, d2, h, w = _frame_pair('nlf_signal', img, img2, ctx, (bg,))
+    d_bg, bgp, bg_pitch, bgv = _bg('nlf_signal', bg, (h, w), ctx)   # d_bg: held until after the call
     d_out = DeviceArray(ctx, (h, w), np.float64)
     ctx._check(ctx._lib.ipa_nlf_signal_dev(
         ctx.handle, d.ptr, dtype_id(d.dtype), d2.ptr if d2 is not None else None, h, w, w, w, bgp,
@@ -78,7 +33,7 @@ def nlf_moments(img, ctx=None):
     non-NaN values and in float64: what camera/NoiseLevelFunction.py:162-173 (_getMinMax) reads
     (ipa_nlf_moments_dev; two passes, no float atomics).  uint8 / uint16 / float32 / float64, host
     array or DeviceArray (other host types go to float64)."""
-    _, ctx, d, h, w = _stage_in('nlf_moments', img, ctx, NLF_DTYPES, _nlf_host)
+    _, ctx, d, h, w = _stage_in('nlf_moments', img, ctx, PIXEL_DTYPES, _px_host)
     m = np.empty(5, np.float64)
     ctx._check(ctx._lib.ipa_nlf_moments_dev(ctx.handle, d.ptr, dtype_id(d.dtype), h, w, w, _dptr(m)),
                'nlf_moments')
@@ -91,9 +46,9 @@ def nlf_bins(img, signal, edges, step, img2=None, bg=None, factor=1.0, rms=False
     edges[n + 1] (both ends inclusive), sums[n] is the sum of |diff| (of diff ** 2 with rms) with
     diff = (img - signal) * factor, or (img - img2) / factor for a pair.  `edges` is the table
     e[k + 1] = e[k] + step.  1 to 2048 bins, NotImplementedError above (ipa_nlf_bins_dev)."""
-    _, ctx, d, d2, h, w = _nlf_frames('nlf_bins', img, img2, ctx, (signal, bg))
+    _, ctx, d, d2, h, w = _frame_pair('nlf_bins', img, img2, ctx, (signal, bg))
     d_sig = _f64_frame('nlf_bins', 'signal', signal, (h, w), ctx)
-    bgp, bg_pitch, bgv = _nlf_bg('nlf_bins', bg, (h, w), ctx)
+    d_bg, bgp, bg_pitch, bgv = _bg('nlf_bins', bg, (h, w), ctx)   # d_bg: held until after the call
     e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
     nbins = e.size - 1
     counts, sums = np.zeros(max(nbins, 0), np.uint64), np.zeros(max(nbins, 0), np.float64)
@@ -112,9 +67,7 @@ def snr_map(signal, nlf=None, noise=None, constant_noise=None, noise_factor=1.0,
     imgs_to_be_averaged.  Host in, host out; DeviceArray in, DeviceArray out."""
     if (nlf is not None) + (noise is not None) + (constant_noise is not None) != 1:
         raise ValueError('snr_map takes exactly one of nlf, noise and constant_noise')
-    dev, ctx, d, h, w = _stage_in('snr_map', signal, ctx, (np.float64,),
-                                  lambda a: np.ascontiguousarray(a, dtype=np.float64),
-                                  (noise, out))
+    dev, ctx, d, h, w = _stage_in('snr_map', signal, ctx, (np.float64,), _f64_host, (noise, out))
     d_noise = None if noise is None else _f64_frame('snr_map', 'noise', noise, (h, w), ctx)
     d_out = _dev_out(ctx, out, (h, w), np.float64) if dev else DeviceArray(ctx, (h, w), np.float64)
     ctx._check(ctx._lib.ipa_snr_map_dev(
@@ -128,7 +81,7 @@ def snr_map(signal, nlf=None, noise=None, constant_noise=None, noise_factor=1.0,
 def snr_bg_median(img, ctx=None):
     """median_filter(img[10:-10:10, 10:-10:10], 3) as float64, the grid under getBackgroundLevel
     (measure/SNR/SNR.py:82-87; ipa_snr_bg_median_dev).  Frames of more than 20 rows and columns."""
-    dev, ctx, d, h, w = _stage_in('snr_bg_median', img, ctx, NLF_DTYPES, _nlf_host)
+    dev, ctx, d, h, w = _stage_in('snr_bg_median', img, ctx, PIXEL_DTYPES, _px_host)
     if h <= 20 or w <= 20:
         raise ValueError('snr_bg_median: img[10:-10:10, 10:-10:10] is empty for shape %s' % ((h, w),))
     gh, gw = -(-(h - 20) // 10), -(-(w - 20) // 10)

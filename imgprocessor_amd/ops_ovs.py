@@ -6,9 +6,10 @@ DeviceArrays stay on the device.
 import numpy as np
 
 from .device import DeviceArray, dtype_id
-from ._staging import _dptr, _is_dev, _stage_in, _stage_out
-from .ops_nlf import NLF_DTYPES, _f64_frame, _nlf_host
-from .ops_dark import MAX_FRAMES, _f64_host, _stack
+from ._staging import (PIXEL_DTYPES, _dptr, _f64_frame, _f64_host, _is_dev, _px_host, _stage_in, _stage_out,
+                       _u8_frame, frame_stack)
+
+MAX_FRAMES = 64   # kOvsMaxN of csrc/ovs.hip
 
 
 def _mats(name, M, n):
@@ -24,24 +25,13 @@ def _mats(name, M, n):
 
 
 def _fits(name, fits, ctx):
-    frames = _stack(name, fits, ctx)
+    frames = frame_stack(name, fits)
     n = frames.shape[0]
     if n < 1:
         raise ValueError('%s: needs at least one fitted image' % name)
     if n > MAX_FRAMES:
         raise NotImplementedError('%s: at most %d fitted images (got %d)' % (name, MAX_FRAMES, n))
     return frames, n
-
-
-def _u8_stack(name, masks, shape, ctx):
-    if _is_dev(masks):
-        d = masks
-    else:
-        d = ctx.to_device(np.ascontiguousarray(np.asarray(masks), dtype=np.uint8))
-    if d.dtype != np.uint8 or tuple(d.shape) != tuple(shape):
-        raise ValueError('%s: the masks must be a uint8 / bool array of shape %s (got %s %s)'
-                         % (name, tuple(shape), d.dtype, tuple(d.shape)))
-    return d
 
 
 def ovs_object(ff, fits, M, ctx=None):
@@ -54,7 +44,7 @@ def ovs_object(ff, fits, M, ctx=None):
     M: (N, 3, 3) destination -> source matrices."""
     frames, n = _fits('ovs_object', fits, ctx)
     m = _mats('ovs_object', M, n)
-    dev, ctx, d, oh, ow = _stage_in('ovs_object', frames, ctx, NLF_DTYPES, _nlf_host, (ff,), ndims=(3,))
+    dev, ctx, d, oh, ow = _stage_in('ovs_object', frames, ctx, PIXEL_DTYPES, _px_host, (ff,), ndims=(3,))
     if not _is_dev(ff):
         ff = np.asarray(ff, dtype=np.float64)
     if len(ff.shape) != 2:
@@ -79,10 +69,10 @@ def ovs_flatfield(obj, fits, masks, M, ff_shape, ctx=None, *, clip=False, sub_st
     [::s, ::s] - what the loop's residuum reads."""
     frames, n = _fits('ovs_flatfield', fits, ctx)
     m = _mats('ovs_flatfield', M, n)
-    dev, ctx, d, oh, ow = _stage_in('ovs_flatfield', frames, ctx, NLF_DTYPES, _nlf_host, (obj, masks),
+    dev, ctx, d, oh, ow = _stage_in('ovs_flatfield', frames, ctx, PIXEL_DTYPES, _px_host, (obj, masks),
                                     ndims=(3,))
     d_obj = _f64_frame('ovs_flatfield', 'the object', obj, (oh, ow), ctx)
-    d_masks = _u8_stack('ovs_flatfield', masks, (n, oh, ow), ctx)
+    d_masks = _u8_frame('ovs_flatfield', 'the masks', masks, (n, oh, ow), ctx)
     fh, fw = int(ff_shape[0]), int(ff_shape[1])
     if fh < 1 or fw < 1:
         raise ValueError('ovs_flatfield: empty flat field %s' % (tuple(ff_shape),))
@@ -116,14 +106,14 @@ def masked_running_mean_update(avg, n, data, mask=None, ctx=None):
             raise ValueError('masked_running_mean_update: average and counts differ in shape')
         d_n = DeviceArray.counts(ctx, (h, w))
         d_n.set(cnt)
-    d_data = data if _is_dev(data) else ctx.to_device(_nlf_host(data))
-    if d_data.dtype not in NLF_DTYPES:
+    d_data = data if _is_dev(data) else ctx.to_device(_px_host(data))
+    if d_data.dtype not in PIXEL_DTYPES:
         raise TypeError('masked_running_mean_update needs uint8 / uint16 / float32 / float64 data (got %s)'
                         % d_data.dtype)
     if tuple(d_data.shape) != (h, w):
         raise ValueError('masked_running_mean_update: data of shape %s for an average of shape %s'
                          % (tuple(d_data.shape), (h, w)))
-    d_mask = None if mask is None else _u8_stack('masked_running_mean_update', mask, (h, w), ctx)
+    d_mask = None if mask is None else _u8_frame('masked_running_mean_update', 'the mask', mask, (h, w), ctx)
     ctx._check(ctx._lib.ipa_masked_running_mean_dev(
         ctx.handle, d_avg.ptr, w, d_n.ptr, w, d_data.ptr, dtype_id(d_data.dtype), w,
         d_mask.ptr if d_mask is not None else None, w, h, w), 'masked_running_mean_update')

@@ -5,9 +5,10 @@
 import numpy as np
 
 from .device import DeviceArray, dtype_id
-from ._staging import _dptr, _stage_in, _stage_out
-from .ops_nlf import NLF_DTYPES, _f64_frame, _nlf_host
-from .ops_dark import MAX_FRAMES, _f64_host, _stack
+from ._staging import (PIXEL_DTYPES, _dptr, _f64_frame, _f64_host, _px_host, _stage_in, _stage_out, _u8_frame,
+                       frame_stack)
+
+MAX_FRAMES = 64   # kTssMaxT of csrc/tss.hip
 
 
 def tss_event_length(stack, times, offset, ascent, error, events=False, ctx=None, *, zero_mask=False):
@@ -20,7 +21,7 @@ def tss_event_length(stack, times, offset, ascent, error, events=False, ctx=None
     error: float64 (h, w), what ops.stack_linregress returns.  events=True: (avlen, events), the
     uint8 (T, h, w) event cube; zero_mask=True (keyword only) appends the uint8 mask avlen == 0.
     Undefined for NaN samples."""
-    frames = _stack('tss_event_length', stack, ctx)
+    frames = frame_stack('tss_event_length', stack)
     t = np.ascontiguousarray(np.asarray(times, dtype=np.float64).ravel())
     n = frames.shape[0]
     if t.size != n:
@@ -29,7 +30,7 @@ def tss_event_length(stack, times, offset, ascent, error, events=False, ctx=None
         raise ValueError('tss_event_length: needs at least 2 frames (got %d)' % n)
     if n > MAX_FRAMES:
         raise NotImplementedError('tss_event_length: at most %d frames (got %d)' % (MAX_FRAMES, n))
-    dev, ctx, d, h, w = _stage_in('tss_event_length', frames, ctx, NLF_DTYPES, _nlf_host,
+    dev, ctx, d, h, w = _stage_in('tss_event_length', frames, ctx, PIXEL_DTYPES, _px_host,
                                   (offset, ascent, error), ndims=(3,))
     planes = [_f64_frame('tss_event_length', name, a, (h, w), ctx)
               for name, a in (('offset', offset), ('ascent', ascent), ('error', error))]
@@ -50,14 +51,9 @@ def tss_finish(mean, mask, ctx=None):
     the maximum, the edge repeated (ipa_tss_finish_dev).  mean: float64, NaN where masked - what
     ops.masked_mean(raw, mask, 7, fill_mask=False, fn='mean') returns; mask: uint8 / bool, raw == 0."""
     dev, ctx, d, h, w = _stage_in('tss_finish', mean, ctx, (np.float64,), _f64_host, (mask,))
-    if dev:
-        if not isinstance(mask, DeviceArray):
-            raise TypeError('tss_finish: device array needs a device mask')
-        d_mask = mask
-    else:
-        d_mask = ctx.to_device(np.ascontiguousarray(mask, dtype=np.uint8))
-    if tuple(d_mask.shape) != (h, w) or d_mask.dtype != np.uint8:
-        raise ValueError('tss_finish: mean and mask must be 2-D arrays of equal shape (mask uint8 / bool)')
+    if dev and not isinstance(mask, DeviceArray):
+        raise TypeError('tss_finish: device array needs a device mask')
+    d_mask = _u8_frame('tss_finish', 'the mask', mask, (h, w), ctx)
     d_out = DeviceArray(ctx, (h, w), np.float64)
     ctx._check(ctx._lib.ipa_tss_finish_dev(ctx.handle, d.ptr, d_mask.ptr, h, w, w, w, d_out.ptr, w),
                'tss_finish')

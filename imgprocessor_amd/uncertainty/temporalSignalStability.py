@@ -27,9 +27,8 @@ order of the values).
 import numpy as np
 
 from .. import ops
-from .._staging import _stage_in, _stage_out
-from ..ops_dark import MAX_FRAMES, _stack
-from ..ops_nlf import NLF_DTYPES, _nlf_host
+from .._staging import PIXEL_DTYPES, _px_host, _stage_in, _stage_out, frame_stack
+from ..ops_tss import MAX_FRAMES
 
 
 def temporalSignalStability(imgs, times, down_scale_factor=1, ctx=None):
@@ -39,7 +38,7 @@ def temporalSignalStability(imgs, times, down_scale_factor=1, ctx=None):
     frames stay on the device and the results are DeviceArrays."""
     if down_scale_factor > 1:
         raise NotImplementedError('temporalSignalStability: down_scale_factor > 1 needs an INTER_AREA resize')
-    imgs = _stack('temporalSignalStability', imgs, ctx)   # a list is stacked once, where its frames live
+    imgs = frame_stack('temporalSignalStability', imgs)   # a list is stacked once, where its frames live
     t = np.asarray(times, dtype=np.float64).ravel()
     if imgs.shape[0] != t.size:
         raise ValueError('temporalSignalStability: %d times for %d frames' % (t.size, imgs.shape[0]))
@@ -48,7 +47,7 @@ def temporalSignalStability(imgs, times, down_scale_factor=1, ctx=None):
     if imgs.shape[0] > MAX_FRAMES:
         raise NotImplementedError('temporalSignalStability: at most %d frames (got %d)' % (MAX_FRAMES, imgs.shape[0]))
     # host frames go up once; everything between the four launches stays on the device
-    dev, ctx, d, _, _ = _stage_in('temporalSignalStability', imgs, ctx, NLF_DTYPES, _nlf_host, ndims=(3,))
+    dev, ctx, d, _, _ = _stage_in('temporalSignalStability', imgs, ctx, PIXEL_DTYPES, _px_host, ndims=(3,))
     offset, ascent, error = ops.stack_linregress(t, d, mx_intensity=np.inf, min_ascent=0)
     raw, zero = ops.tss_event_length(d, t, offset, ascent, error, zero_mask=True)
     avlen = ops.tss_finish(ops.masked_mean(raw, zero, 7, fill_mask=False, fn='mean'), zero)

@@ -278,3 +278,150 @@ def test_masked_fills_refuse_a_mask_of_another_shape(stub, dev):
         for name, run in fills.items():
             with pytest.raises(ValueError):          # a device mask is read as bytes: uint8 only
                 run(up(f['grid']), up(f['grid']))
+
+
+# --------------------------------------------------------------- the calibration families
+class PoolContext(StubContext):
+    """a stub whose released blocks come back: pooled by size, last in first out, as Context._alloc
+    and _release pool them.  An upload that is dropped before the call hands its address to the
+    next allocation of that size."""
+
+    def __init__(self):
+        StubContext.__init__(self)
+        self._pool = {}
+
+    def _alloc(self, nbytes):
+        blocks = self._pool.get(nbytes)
+        return blocks.pop() if blocks else StubContext._alloc(self, nbytes)
+
+    def _release(self, ptr, nbytes):
+        self._pool.setdefault(nbytes, []).append(ptr)
+
+
+CAL_N, CAL_HW, CAL_SMALL = 3, (37, 53), (4, 5)
+
+
+def calibration_cases(ctx):
+    """[(label, thunk)]: every calibration op once, every array argument a HOST array - the frames
+    and all side arrays (bg, signal, noise, ascent, avg, small, obj, masks, the three TSS planes)"""
+    rng = np.random.default_rng(11)
+    h, w = CAL_HW
+    img, img2, bg, sig, plane = (rng.random(CAL_HW) for _ in range(5))
+    stack = (rng.random((CAL_N,) + CAL_HW) * 1000).astype(np.uint16)
+    masks = (rng.random((CAL_N,) + CAL_HW) < 0.2).astype(np.uint8)
+    times = np.arange(CAL_N, dtype=np.float64)
+    mats = np.tile(np.eye(3), (CAL_N, 1, 1))
+    edges = np.linspace(0.0, 1.0, 9)
+    nlf = (0.01, 0.0, 0.1)
+    return [
+        ('nlf_signal bg', lambda: ops.nlf_signal(img, bg=bg, ctx=ctx)),
+        ('nlf_signal pair bg', lambda: ops.nlf_signal(img, img2, bg=bg, ctx=ctx)),
+        ('nlf_moments', lambda: ops.nlf_moments(img, ctx=ctx)),
+        ('nlf_bins signal bg', lambda: ops.nlf_bins(img, sig, edges, 0.125, bg=bg, ctx=ctx)),
+        ('nlf_bins pair signal bg', lambda: ops.nlf_bins(img, sig, edges, 0.125, img2=img2, bg=bg, ctx=ctx)),
+        ('snr_map noise', lambda: ops.snr_map(sig, noise=plane, ctx=ctx)),
+        ('snr_bg_median', lambda: ops.snr_bg_median(img, ctx=ctx)),
+        ('pair_min', lambda: ops.pair_min(img, img2, ctx=ctx)),
+        ('nlf_threshold', lambda: ops.nlf_threshold(img, nlf, ctx=ctx)),
+        ('stack_linregress', lambda: ops.stack_linregress(times, stack, ctx=ctx)),
+        ('dark_current_eval ascent', lambda: ops.dark_current_eval(img, plane, 2.0, 255, ctx=ctx)),
+        ('cast_trunc', lambda: ops.cast_trunc(img, np.uint16, ctx=ctx)),
+        ('stack_mean', lambda: ops.stack_mean(stack, ctx=ctx)),
+        ('stack_mean list', lambda: ops.stack_mean(list(stack), ctx=ctx)),
+        ('luma', lambda: ops.luma(rng.random(CAL_HW + (3,)), ctx=ctx)),
+        ('strided_median_max', lambda: ops.strided_median_max(img, ctx=ctx)),
+        ('strided_min', lambda: ops.strided_min(img, 3, 2, ctx=ctx)),
+        ('flat_scale bg', lambda: ops.flat_scale(img, bg=bg, div=2.0, ctx=ctx)),
+        ('nlf_lower_mask avg', lambda: ops.nlf_lower_mask(stack[0], plane, nlf, ctx=ctx)),
+        ('sens_shrink bg', lambda: ops.sens_shrink(img, bg=bg, f=10, ctx=ctx)),
+        ('sens_accumulate small bg', lambda: ops.sens_accumulate(
+            img, rng.random(CAL_SMALL), ctx.to_device(np.zeros(CAL_HW)), bg=bg, first=True, ctx=ctx)),
+        ('tss_event_length planes', lambda: ops.tss_event_length(
+            stack, times, img, plane, sig, events=True, ctx=ctx, zero_mask=True)),
+        ('tss_finish mask', lambda: ops.tss_finish(img, masks[0], ctx=ctx)),
+        ('ovs_object ff', lambda: ops.ovs_object(rng.random((41, 59)), stack, mats, ctx=ctx)),
+        ('ovs_flatfield obj masks', lambda: ops.ovs_flatfield(img, stack, masks, mats, (41, 59), ctx=ctx,
+                                                              sub_step=10)),
+        ('masked_running_mean_update', lambda: ops.masked_running_mean_update(
+            img, np.ones(CAL_HW, np.int32), stack[0], masks[0], ctx=ctx)),
+    ]
+
+
+CAL_LABELS = [label for label, _ in calibration_cases(None)]
+
+
+def test_every_calibration_op_has_a_host_case():
+    names = set()
+    for mod in ('ops_nlf', 'ops_dark', 'ops_flat', 'ops_tss', 'ops_ovs'):
+        full = 'imgprocessor_amd.' + mod
+        names |= {n for n, fn in vars(ops).items() if inspect.isfunction(fn) and fn.__module__ == full}
+    assert names - {'nlf_params'} == {label.split()[0] for label in CAL_LABELS}
+
+
+@pytest.mark.parametrize('label', CAL_LABELS)
+def test_host_side_arrays_outlive_their_call(label):
+    """Within one ipa_*_dev call no two arguments are the same allocation.  A host side array is
+    uploaded into a temporary; if the wrapper lets go of it before the call, the pool hands its
+    block to the result and the library sees the input and the output at one address."""
+    ctx = PoolContext()
+    dict(calibration_cases(ctx))[label]()
+    blocks = {a for a, _ in ctx.allocs}
+    dev_calls = [(n, a) for n, a in ctx._lib.calls if n.endswith('_dev')]
+    assert dev_calls, '%s reached no device entry point' % label
+    for name, args in dev_calls:
+        check_call(name, args)
+        got = [a.value for a in args if isinstance(a, C.c_void_p) and a.value in blocks]
+        assert len(set(got)) == len(got), '%s: %s was handed one block twice: %s' % (
+            label, name, ['%#x' % v for v in got])
+
+
+def test_frame_stack_normalises_stacks_and_lists():
+    from imgprocessor_amd._staging import frame_stack
+    ctx = StubContext()
+    rng = np.random.default_rng(5)
+    host = (rng.random((CAL_N,) + CAL_HW) * 255).astype(np.uint8)
+    # host: a stack as it is, a list through np.stack; nothing is allocated
+    assert frame_stack('t', host) is host
+    got = frame_stack('t', [f for f in host])
+    assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and np.array_equal(got, host)
+    assert not ctx.allocs and not ctx._lib.calls
+    # device: a stack as it is, a list gathered into ONE allocation by n device copies
+    d_stack = ctx.to_device(host)
+    assert frame_stack('t', d_stack) is d_stack
+    frames = [ctx.to_device(f) for f in host]
+    del ctx.allocs[:], ctx._lib.calls[:]
+    st = frame_stack('t', frames)
+    assert isinstance(st, DeviceArray) and st.shape == host.shape and st.dtype == np.uint8 and st.ctx is ctx
+    assert ctx.allocs == [(st.ptr.value, host.nbytes)]
+    copies = [(args[1].value, args[2].value, args[3]) for name, args in ctx._lib.calls if name == 'ipa_memcpy_d2d']
+    assert [n for n, _ in ctx._lib.calls] == ['ipa_memcpy_d2d'] * CAL_N
+    assert copies == [(st.ptr.value + k * host[0].nbytes, f.ptr.value, host[0].nbytes) for k, f in enumerate(frames)]
+    # colour frames where the caller allows them
+    rgb = [ctx.to_device(np.zeros(CAL_HW + (3,), np.float32)) for _ in range(2)]
+    assert frame_stack('t', rgb, ndims=(2, 3)).shape == (2,) + CAL_HW + (3,)
+    with pytest.raises(ValueError):
+        frame_stack('t', rgb)
+    with pytest.raises(ValueError):
+        frame_stack('t', host[0])                                  # one frame is no stack
+    # a mix is a TypeError, device frames of different shape or dtype a ValueError
+    for mixed in ([frames[0], host[1]], [host[0], frames[1]]):
+        with pytest.raises(TypeError):
+            frame_stack('t', mixed)
+    with pytest.raises(ValueError):
+        frame_stack('t', [frames[0], ctx.to_device(host[1][:, :50])])
+    with pytest.raises(ValueError):
+        frame_stack('t', [frames[0], ctx.to_device(host[1].astype(np.uint16))])
+    with pytest.raises(ValueError):
+        frame_stack('t', [frames[0], StubContext().to_device(host[1])])
+    with pytest.raises(ValueError):
+        frame_stack('t', [host[0], host[1][:, :50]])
+
+
+@pytest.mark.parametrize('family', ['ops_nlf', 'ops_dark', 'ops_flat', 'ops_tss', 'ops_ovs'])
+def test_an_ops_family_imports_no_layer_built_on_it(family):
+    import subprocess
+    import sys
+    code = ('import sys, imgprocessor_amd.%s\n'
+            'up = [m for m in ("features", "camera", "uncertainty") if "imgprocessor_amd." + m in sys.modules]\n'
+            'assert not up, up' % family)
+    subprocess.check_call([sys.executable, '-c', code])

@@ -67,6 +67,7 @@ def test_signal_is_scipys_median(ctx, shape):
         bg = np.random.default_rng(5).uniform(0, 30, shape)
         d = ops.nlf_signal(ctx.to_device(a), bg=ctx.to_device(bg))
         assert d.dtype == np.float64 and same(d.get(), ref.signal_of(a, None, bg)), (shape, dt, 'device')
+        assert same(ops.nlf_signal(a, bg=bg), ref.signal_of(a, None, bg)), (shape, dt, 'host bg array')
 
 
 def test_pitched_rows(ctx):
@@ -146,6 +147,11 @@ def test_bins_on_ragged_shapes(ctx, shape):
             got = ops.nlf_bins(a, sig, e, step, img2=img2, factor=factor, rms=rms)
             check_bins(got, ref.loop_bins(sig, d * d if rms else np.abs(d), e),
                        '%dx%d %s %s' % (h, w, np.dtype(dt).name, form))
+        bg = np.random.default_rng(6).uniform(0, 3, shape)     # a host background array
+        sig = ref.signal_of(a, None, bg)
+        check_bins(ops.nlf_bins(a, sig, e, step, bg=bg, factor=ref.F_NOISE_WITH_MEDIAN),
+                   ref.loop_bins(sig, np.abs(ref.diff_of(a, sig, None, bg)), e),
+                   '%dx%d %s host bg' % (h, w, np.dtype(dt).name))
 
 
 def test_idle_workgroups_write_zeros(ctx, N):
