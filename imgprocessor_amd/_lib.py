@@ -44,6 +44,9 @@ NLF_BOUNDED_SQRT, NLF_CLIPPED_POLY, NLF_CONSTANT = range(3)
 # ipa_extremum_mode of ipa_strided_extremum_dev
 EXTREMUM_MEDIAN_MAX, EXTREMUM_MIN = range(2)
 
+# ipa_poly_mode of ipa_poly2d_eval_dev
+POLY_FILL, POLY_ALL, POLY_GRID = range(3)
+
 # IPA_REMAP_PATH_* bits of the read-only tuning word "remap_path"
 (REMAP_PATH_GATHER, REMAP_PATH_REST, REMAP_PATH_RING, REMAP_PATH_TILE, REMAP_PATH_TILE_MAP,
  REMAP_PATH_STORED, REMAP_PATH_U8_LZ_LDS, REMAP_PATH_STRIP, REMAP_PATH_STRIP_INT, REMAP_PATH_LENS_MAP,
@@ -177,6 +180,10 @@ PROTOTYPES = {
     'ipa_ovs_flatfield_dev': [_vp, _vp, _l, _vp, _i, _i, _i, _i, _l, _l, _vp, _l, _l, _dp, _vp, _i, _i, _l,
                               _vp, _l, _i, _vp, _i, _l],
     'ipa_masked_running_mean_dev': [_vp, _vp, _l, _vp, _l, _vp, _i, _l, _vp, _l, _i, _i],
+    'ipa_poly2d_moments_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _i, _dp],
+    'ipa_poly2d_eval_dev': [_vp, _dp, _i, _i, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp, _i, _i, _l, _vp, _l, _dp],
+    'ipa_high_grad_dev': [_vp, _vp, _i, _i, _i, _l, _d, _i, _vp, _l, _dp],
+    'ipa_clip01_dev': [_vp, _vp, _i, _i, _i, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

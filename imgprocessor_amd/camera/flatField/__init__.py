@@ -2,3 +2,5 @@ from .vignettingFromDiscreteSteps import rescaleToGrid  # noqa: F401
 from .flatFieldFromCloseDistance import (flatFieldFromCloseDistance,  # noqa: F401
                                          flatFieldFromCloseDistance2)
 from .sensitivity import sensitivity  # noqa: F401
+from .postProcessing import postProcessing, ppMETHODS  # noqa: F401
+from .postprocessing.polynomial import polynomial  # noqa: F401

@@ -5,3 +5,4 @@ from .interpolate2dUnstructuredIDW import interpolate2dUnstructuredIDW  # noqa: 
 from .interpolateCircular2dStructuredIDW import interpolateCircular2dStructuredIDW  # noqa: F401
 from .interpolate2dStructuredCrossAvg import interpolate2dStructuredCrossAvg  # noqa: F401
 from .interpolate2dStructuredPointSpreadIDW import interpolate2dStructuredPointSpreadIDW  # noqa: F401
+from .polyfit2d import polyfit2dGrid  # noqa: F401

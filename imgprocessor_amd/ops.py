@@ -24,6 +24,9 @@ from .ops_flat import (stack_mean, luma, strided_median_max, strided_min, flat_s
 from .ops_tss import tss_event_length, tss_finish  # noqa: F401
 # the object / vignetting separation family lives in ops_ovs.py
 from .ops_ovs import ovs_object, ovs_flatfield, masked_running_mean_update  # noqa: F401
+# the 2-D polynomial fit family lives in ops_poly.py
+from .ops_poly import (poly2d_moments, poly2d_gram, poly2d_solve, poly2d_eval, high_grad_window,  # noqa: F401
+                       high_grad_mask, clip01)
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -963,6 +963,61 @@ int ipa_masked_running_mean_dev(ipa_ctx* ctx, double* d_avg, long avg_pitch, int
                                 int dtype, long data_pitch, const unsigned char* d_mask, long mask_pitch, int h,
                                 int w);
 
+/* ---- 2-D polynomial fits of masked frames (csrc/poly.hip) ---------------------------------------
+ * interpolate/polyfit2d.py (polyfit2dGrid) and camera/flatField/postprocessing/polynomial.py.  The
+ * reference fits raw monomials x**i * y**j by lstsq on an (n_valid, (o+1)^2) design matrix; here the
+ * basis is T_j(v) T_i(u), Chebyshev polynomials (T_0 = 1, T_1 = u, T_k = 2 u T_{k-1} - T_{k-2}) of
+ *   u = (2 x - (w - 1)) / (w - 1),  v = (2 y - (h - 1)) / (h - 1)   (0 for a dimension of size 1):
+ * the same polynomial space in a basis that stays well conditioned.  Frames are float32 / float64
+ * (anything else IPA_ERR_UNSUPPORTED), order is 0 .. 5 (above: IPA_ERR_UNSUPPORTED), masks uint8
+ * with non-zero = invalid.  The (o+1)^2 x (o+1)^2 system is the caller's to solve. */
+typedef enum {
+  IPA_POLY_FILL,   /* replace the masked pixels (a NULL mask: every pixel); the others are copied */
+  IPA_POLY_ALL,    /* write every pixel */
+  IPA_POLY_GRID    /* evaluate at an outgrid of pixel positions */
+} ipa_poly_mode;
+
+/* polyfit2d.py:13-18 with :46-49 - the sums of the normal equations over the VALID pixels (d_mask
+ * NULL: all; a masked pixel is selected out, its value - NaN in the reference's own example - never
+ * enters a sum).  moments (host): n = 2 order + 1, k = order + 1,
+ *   moments[b n + a]           = sum T_b(v) T_a(u)      a, b <= 2 order
+ *   moments[n n + j k + i]     = sum z T_j(v) T_i(u)    i, j <= order
+ *   moments[n n + k k]         = the number of valid pixels.
+ * The Gram matrix follows from T_i T_k = (T_{i+k} + T_{|i-k|}) / 2.  Per-workgroup partial sums are
+ * added in a fixed order by a second launch, no float atomics: two calls give identical bits.
+ * Synchronises the stream. */
+int ipa_poly2d_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                           const unsigned char* d_mask, long mask_pitch, int order, double* moments);
+
+/* polyfit2d.py:22-28 with :50-64 - the polynomial with the (order+1)^2 host coefficients coef[j k + i]
+ * of T_j(v) T_i(u), evaluated in double in the operation order csrc/poly.hip spells out and rounded
+ * once into the frame's type.  h x w is the frame of the coordinate map in every mode.
+ *   IPA_POLY_FILL  d_out = d_in with the pixels under d_mask replaced (d_mask NULL: all of them);
+ *                  d_out may be d_in itself (same pointer and pitch: in place)
+ *   IPA_POLY_ALL   every pixel of d_out (h x w); d_in may be NULL, d_mask is ignored
+ *   IPA_POLY_GRID  d_out is gh x gw, pixel (r, c) evaluated at the position (d_gy, d_gx)[r][c] (float64,
+ *                  grid_pitch); positions outside the frame extrapolate; d_in and d_mask are ignored
+ * residuum (host, may be NULL; FILL and ALL with d_in): sum |new - old| over the replaced pixels, new
+ * as stored - polynomial.py:37 times the frame's size.  Per-tile partials added in a fixed order;
+ * asking for it synchronises the stream.  An overlap of d_out with anything but an in-place d_in is
+ * IPA_ERR_BAD_ARG. */
+int ipa_poly2d_eval_dev(ipa_ctx* ctx, const double* coef, int order, int mode, const void* d_in, int dtype, int h,
+                        int w, long in_pitch, const unsigned char* d_mask, long mask_pitch, const double* d_gy,
+                        const double* d_gx, int gh, int gw, long grid_pitch, void* d_out, long out_pitch,
+                        double* residuum);
+
+/* polynomial.py:10-14 (_highGrad) - d_mask = maximum_filter(|laplace(img, mode='reflect')| > threshold,
+ * size): the Laplacian per axis c * (-2) + (l + r) in double, rounded to the frame's type, axis 0 plus
+ * axis 1 and the comparison in the frame's type (scipy's arithmetic); then the separable dilation by
+ * a window of offsets -(size / 2) .. size - size / 2 - 1, 1 <= size <= 31 (above:
+ * IPA_ERR_UNSUPPORTED).  d_mask: uint8 0 / 1, must not overlap the frame; *count (host): its sum.
+ * Synchronises the stream. */
+int ipa_high_grad_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, double threshold, int size,
+                      unsigned char* d_mask, long mask_pitch, double* count);
+
+/* polynomial.py:49 - np.clip(img, 0, 1, out=img): in place, NaN stays. */
+int ipa_clip01_dev(ipa_ctx* ctx, void* d_img, int dtype, int h, int w, long pitch);
+
 #ifdef __cplusplus
 }
 #endif
