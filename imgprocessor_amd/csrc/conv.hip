@@ -14,17 +14,8 @@
 #include "common.hpp"
 #include "conv_paths.hpp"
 #include "conv_tile.hpp"
-#include "wave_stencil.hpp"
-
-// float32 K x K filter on the wave-marching skeleton (instantiated per K in fused_k*.hip)
-int ipa_wave_conv_launch_k3(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double*, int);
-int ipa_wave_conv_launch_k5(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double*, int);
-int ipa_wave_conv_launch_k7(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double*, int);
-int ipa_wave_conv_launch_k9(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double*, int);
-int ipa_wave_conv_launch_k11(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double*, int);
-// float32 separable K+K filter on the same skeleton (wave_sep.hip); returns 1 if not covered
-int ipa_wave_sep_launch(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* ky,
-                        int nky, const double* kx, int nkx, int n_frames, float xcval);
+#include "launch.hpp"
+#include "wave_stencil.hpp"   // WaveParams, LoadRowSrc and the wave launchers of the plain filters
 
 namespace ipa {
 
@@ -340,74 +331,114 @@ extend_kernel(const T* __restrict__ src, int h, int w, long spitch, int px, int 
 
 using namespace ipa;
 
+// The frames of a call as both entry points receive them (pitches and frame strides in elements), with what every
+// kernel's parameters repeat of them: vec_in / vec_out, computed once per call.
+struct Frames {
+  const void* src;
+  void* dst;
+  int h, w;
+  long spitch, dpitch;
+  int n;
+  long sstride, dstride;
+  int bx, by;
+  double cval;
+  int vec_in, vec_out;
+};
+static Frames frames_of(const void* src, void* dst, int dtype, int h, int w, long spitch, long dpitch, int n,
+                        long sstride, long dstride, int bx, int by, double cval) {
+  const size_t es = ipa_dtype_size(dtype);
+  return {src, dst, h, w, spitch, dpitch, n, sstride, dstride, bx, by, cval,
+          aligned_rows(src, spitch, sstride, n, es, IPA_VEC_ALIGN), aligned_rows(dst, dpitch, dstride, n, es, IPA_VEC_ALIGN)};
+}
+
+// the members ConvParams and SepParams share
+template <typename P>
+static P tile_params(const Frames& f) {
+  P p;
+  p.src = (const char*)f.src; p.dst = (char*)f.dst;
+  p.src_frame_elems = f.sstride; p.dst_frame_elems = f.dstride;
+  p.h = f.h; p.w = f.w; p.spitch = f.spitch; p.dpitch = f.dpitch;
+  p.bx = f.bx; p.by = f.by; p.cval = f.cval;
+  p.tiles_x = (unsigned)((f.w + kTileW - 1) / kTileW);
+  p.tiles = p.tiles_x * (unsigned)((f.h + kTileH - 1) / kTileH);
+  p.vec_in = f.vec_in; p.vec_out = f.vec_out;
+  return p;
+}
+
+// the parameters of a wave launcher (wave_stencil.hpp) for plain float32 rows; the launcher adds its strips and grid
+static void wave_rows(const Frames& f, WaveParams& wp, LoadRowSrc& src) {
+  wp.dst = (char*)f.dst; wp.dst_frame_elems = f.dstride;
+  wp.dh = f.h; wp.dw = f.w; wp.dpitch = f.dpitch;
+  wp.cbx = f.bx; wp.cby = f.by;
+  wp.vec_out = f.vec_out;
+  src.base = (const float*)f.src; src.frame_elems = f.sstride; src.pitch = f.spitch;
+  src.vec_in = f.vec_in; src.cval = (float)f.cval;
+}
+
+// No kernel is listed for a size that conv2d_path sent here: the two disagree.  kNotCovered stays inside.
+static int covered(ipa_ctx* ctx, int rc, const char* what, int k) {
+  IPA_REQUIRE(ctx, rc != kNotCovered, "internal error: no %s kernel for %dx%d", what, k, k);
+  return rc;
+}
+
 template <typename T, int K>
-static void launch_conv(ipa_ctx* ctx, const ConvParams& p, const double* kernel, int n_frames) {
+static int launch_conv(ipa_ctx* ctx, const ConvParams& p, const double* kernel, int n_frames) {
   Weights<T, K * K> w;
   for (int i = 0; i < K * K; i++) w.w[i] = (T)kernel[i];
   using G = conv_geom<K>;
   size_t lds = (size_t)lds_rows<K>() * G::LW * sizeof(T);
   dim3 grid(p.tiles, (unsigned)n_frames), block(32, 8);
-  hipLaunchKernelGGL((conv_kernel<T, K, K>), grid, block, lds, ctx->stream, p, w);
+  return launch(ctx, conv_kernel<T, K, K>, grid, block, lds, p, w);
 }
 
+// the five translation units of the float32 K x K wave filter, each beside its K
+// (7x7 with streamed coefficients measured slower here: 285 vs 278 us)
+static const struct {
+  int k;
+  int (*launch)(ipa_ctx*, const WaveParams&, const LoadRowSrc&, const double*, int);
+} kWaveConv[] = {{3, ipa_wave_conv_launch_k3}, {5, ipa_wave_conv_launch_k5}, {7, ipa_wave_conv_launch_k7},
+                 {9, ipa_wave_conv_launch_k9}, {11, ipa_wave_conv_launch_k11}};
+
 template <typename T>
-static int conv_typed(ipa_ctx* ctx, ConvParams& p, const double* kernel, int kh, int kw,
-                      int n_frames) {
+static int conv_typed(ipa_ctx* ctx, const Frames& f, const uint8_t* mask, long mask_pitch, const double* kernel,
+                      int kh, int kw) {
+  constexpr bool kF32 = sizeof(T) == 4;
+  ConvParams p = tile_params<ConvParams>(f);
+  p.mask = mask; p.mask_pitch = mask_pitch;
   // wave / LDS tile / generic: conv2d_path (conv_paths.hpp)
-  const int path = conv2d_path(sizeof(T) == 4 ? IPA_F32 : IPA_F64, kh, kw, p.mask != nullptr,
-                               ctx->tune.big_wave != 0);
-  if constexpr (sizeof(T) == 4) {
-    // float32: the wave-marching stencil (wave_stencil.hpp)
-    // (masked filtering stays on the LDS-tiled kernel; so do 9x9 / 11x11 with the context knob big_wave = 0,
-    // the tuning knob that A/Bs wave_conv_big.hip against it: 334 vs 375 us, 428 vs 487 us)
-    if (path == kConvWave) {
-      WaveParams wp;
-      wp.dst = p.dst; wp.dst_frame_elems = p.dst_frame_elems;
-      wp.dh = p.h; wp.dw = p.w; wp.dpitch = p.dpitch;
-      wp.cbx = p.bx; wp.cby = p.by;
-      wp.vec_out = p.vec_out;
-      LoadRowSrc src;
-      src.base = (const float*)p.src; src.frame_elems = p.src_frame_elems; src.pitch = p.spitch;
-      src.vec_in = p.vec_in; src.cval = (float)p.cval;
-      switch (kh) {
-        case 3: ipa_wave_conv_launch_k3(ctx, wp, src, kernel, n_frames); break;
-        case 5: ipa_wave_conv_launch_k5(ctx, wp, src, kernel, n_frames); break;
-        // (7x7 with streamed coefficients measured slower here: 285 vs 278 us)
-        case 7: ipa_wave_conv_launch_k7(ctx, wp, src, kernel, n_frames); break;
-        case 9: ipa_wave_conv_launch_k9(ctx, wp, src, kernel, n_frames); break;
-        default: ipa_wave_conv_launch_k11(ctx, wp, src, kernel, n_frames); break;
+  switch (conv2d_path(kF32 ? IPA_F32 : IPA_F64, kh, kw, mask != nullptr, ctx->tune.big_wave != 0)) {
+    case kConvWave:
+      // float32 only: the wave-marching stencil (wave_stencil.hpp)
+      // (masked filtering stays on the LDS-tiled kernel; so do 9x9 / 11x11 with the context knob big_wave = 0,
+      // the tuning knob that A/Bs wave_conv_big.hip against it: 334 vs 375 us, 428 vs 487 us)
+      if constexpr (kF32) {
+        WaveParams wp;
+        LoadRowSrc src;
+        wave_rows(f, wp, src);
+        for (const auto& e : kWaveConv)
+          if (e.k == kh) return e.launch(ctx, wp, src, kernel, f.n);
       }
-      IPA_HIP(ctx, hipGetLastError());
-      return IPA_OK;
+      return covered(ctx, kNotCovered, "wave", kh);
+    case kConvTile: {
+      auto tile = [&](auto K) { return launch_conv<T, decltype(K)::value>(ctx, p, kernel, f.n); };
+      // (float64: the tile kernel is instantiated to 7x7)
+      if constexpr (kF32) return covered(ctx, pick<3, 5, 7, 9, 11>(kh, tile), "tile", kh);
+      else return covered(ctx, pick<3, 5, 7>(kh, tile), "tile", kh);
     }
-  }
-  if (path == kConvTile) {
-    switch (kh) {
-      case 3: launch_conv<T, 3>(ctx, p, kernel, n_frames); break;
-      case 5: launch_conv<T, 5>(ctx, p, kernel, n_frames); break;
-      case 7: launch_conv<T, 7>(ctx, p, kernel, n_frames); break;
-      case 9:
-        if constexpr (sizeof(T) == 4) launch_conv<T, 9>(ctx, p, kernel, n_frames);
-        break;
-      case 11:
-        if constexpr (sizeof(T) == 4) launch_conv<T, 11>(ctx, p, kernel, n_frames);
-        break;
+    case kConvGeneric: {
+      // weights through the table arena
+      std::vector<T> hw((size_t)kh * kw);
+      for (size_t i = 0; i < hw.size(); i++) hw[i] = (T)kernel[i];
+      void* dw = nullptr;
+      int rc = ipa_tab_upload(ctx, hw.data(), hw.size() * sizeof(T), &dw);
+      if (rc) return rc;
+      dim3 grid((p.w + 63) / 64, (p.h + 3) / 4, (unsigned)f.n), block(64, 4);
+      return launch(ctx, conv_generic_kernel<T>, grid, block, 0, p, dw, kh, kw);
     }
-    IPA_HIP(ctx, hipGetLastError());
-    return IPA_OK;
+    default:   // kConvRefused: more taps than the generic kernel takes
+      ipa_set_error(ctx, "kernel too large (%dx%d)", kh, kw);
+      return IPA_ERR_BAD_ARG;
   }
-  // generic: weights through the table arena
-  IPA_REQUIRE(ctx, (long)kh * kw <= kConvGenericMaxTaps, "kernel too large (%dx%d)", kh, kw);
-  IPA_REQUIRE(ctx, n_frames <= 65535, "n_frames too large");
-  std::vector<T> hw((size_t)kh * kw);
-  for (size_t i = 0; i < hw.size(); i++) hw[i] = (T)kernel[i];
-  void* dw = nullptr;
-  int rc = ipa_tab_upload(ctx, hw.data(), hw.size() * sizeof(T), &dw);
-  if (rc) return rc;
-  dim3 grid((p.w + 63) / 64, (p.h + 3) / 4, (unsigned)n_frames), block(64, 4);
-  hipLaunchKernelGGL((conv_generic_kernel<T>), grid, block, 0, ctx->stream, p, (const T*)dw, kh, kw);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
 }
 
 static int check_border(ipa_ctx* ctx, int b) {
@@ -442,23 +473,52 @@ static int channels_launch(ipa_ctx* ctx, const void* d_src, int dtype, int h, in
   IPA_REQUIRE(ctx, d_src && d_dst && h > 0 && w > 0 && ch > 0, "bad arguments");
   IPA_REQUIRE(ctx, ipitch >= (long)w * ch && ppitch >= w && pstride >= (long)(h - 1) * ppitch + w,
               "pitch / plane stride smaller than the image");
+  IPA_REQUIRE(ctx, known_dtype(dtype), "unknown dtype %d", dtype);
   dim3 grid((w + 63) / 64, (h + 3) / 4), block(256);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-#define IPA_CH(T)                                                                                   \
-  hipLaunchKernelGGL((channels_kernel<T, TO_PLANES>), grid, block, 0, ctx->stream, (const T*)d_src, \
-                     (T*)d_dst, h, w, ch, ipitch, ppitch, pstride)
-  switch (dtype) {
-    case IPA_U8: IPA_CH(uint8_t); break;
-    case IPA_U16: IPA_CH(uint16_t); break;
-    case IPA_F32: IPA_CH(float); break;
-    case IPA_F64: IPA_CH(double); break;
-    default: IPA_REQUIRE(ctx, false, "unknown dtype %d", dtype);
-  }
-#undef IPA_CH
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return launch(ctx, channels_kernel<decltype(t), TO_PLANES>, grid, block, 0, d_src, d_dst, h, w, ch, ipitch, ppitch,
+                  pstride);
+  });
 }
 
+// the LDS separable kernel (kSepLds; kSepLdsBig: with the dynamic-LDS opt-in)
+static int sep_lds_launch(ipa_ctx* ctx, const Frames& f, int dtype, const double* ky, int nky, const double* kx,
+                          int nkx, bool opt_in) {
+  SepParams p = tile_params<SepParams>(f);
+  p.nky = nky; p.nkx = nkx; p.hy = nky / 2; p.hx = nkx / 2;
+  p.hxa = ((p.hx + 3) / 4) * 4;
+  static_assert(kSepLdsGiveUp <= 160 * 1024, "the LDS kernel's planes within the 160 KiB of a workgroup");
+  const size_t lds = sepconv_lds(ipa_dtype_size(dtype), nky, nkx);
+  dim3 grid(p.tiles, (unsigned)f.n), block(32, 8);
+  return by_float(dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    SepWeights<T> sw;
+    for (int i = 0; i < nky; i++) sw.ky[i] = (T)ky[i];
+    for (int i = 0; i < nkx; i++) sw.kx[i] = (T)kx[i];
+    if (opt_in)
+      IPA_HIP(ctx, hipFuncSetAttribute((const void*)sepconv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+    return launch(ctx, sepconv_kernel<T>, grid, block, lds, p, sw);
+  });
+}
+
+// The host-pointer variants: the frames (and a mask, or null) staged in through the workspace, run(in, out, mask) on
+// the device copies - contiguous frames of h x w -, the result staged out.
+template <typename Run>
+static int staged(ipa_ctx* ctx, const void* src, int dtype, int h, int w, int n_frames, const uint8_t* mask, void* dst,
+                  const Run& run) {
+  if (!ctx) return IPA_ERR_BAD_ARG;
+  IPA_REQUIRE(ctx, src && dst && h > 0 && w > 0 && n_frames >= 1, "bad arguments");
+  size_t es = ipa_dtype_size(dtype);
+  IPA_REQUIRE(ctx, es, "unknown dtype");
+  const size_t ib = (size_t)h * w * es * n_frames, mb = mask ? (size_t)h * w : 0;
+  char* d[3];   // in, out, mask (null without one)
+  int rc = ipa_stage_in(ctx, {{src, ib}, {nullptr, ib}, {mask, mb}}, d);
+  if (rc) return rc;
+  rc = run(d[0], d[1], (const uint8_t*)d[2]);
+  if (rc) return rc;
+  return ipa_stage_out(ctx, {{dst, d[1], ib}});
+}
 
 extern "C" {
 
@@ -494,20 +554,12 @@ int ipa_conv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, lon
                                src_frame_stride, dst_frame_stride, border_y, border_x, border_value);
     }
   }
-  size_t es = ipa_dtype_size(dtype);
-  ConvParams p;
-  p.src = (const char*)d_src; p.dst = (char*)d_dst;
-  p.mask = d_mask; p.mask_pitch = mask_pitch;
-  p.src_frame_elems = src_frame_stride; p.dst_frame_elems = dst_frame_stride;
-  p.h = h; p.w = w; p.spitch = src_pitch; p.dpitch = dst_pitch;
-  p.bx = border_x; p.by = border_y; p.cval = border_value;
-  p.tiles_x = (unsigned)((w + kTileW - 1) / kTileW);
-  p.tiles = p.tiles_x * (unsigned)((h + kTileH - 1) / kTileH);
-  p.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
-  p.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
+  const Frames f = frames_of(d_src, d_dst, dtype, h, w, src_pitch, dst_pitch, n_frames, src_frame_stride,
+                             dst_frame_stride, border_x, border_y, border_value);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (dtype == IPA_F32) return conv_typed<float>(ctx, p, kernel, kh, kw, n_frames);
-  return conv_typed<double>(ctx, p, kernel, kh, kw, n_frames);
+  return by_float(dtype, [&](auto t) {
+    return conv_typed<decltype(t)>(ctx, f, d_mask, mask_pitch, kernel, kh, kw);
+  });
 }
 
 int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, long src_pitch,
@@ -518,36 +570,8 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   IPA_REQUIRE(ctx, d_src && d_dst, "null pointer");
   IPA_REQUIRE(ctx, h > 0 && w > 0, "empty image");
   IPA_REQUIRE(ctx, nky >= 0 && nkx >= 0 && (nky == 0 || ky) && (nkx == 0 || kx), "bad kernel args");
-  {
-    // long kernels (e.g. sigma = 11 -> 89 taps, filters/standardDeviation.py:23) do not fit
-    // the kernarg table / LDS planes: run the two axes as two launches of the generic
-    // correlation with the intermediate (rounded to the image dtype, like scipy) in a
-    // temporary device buffer (sepconv_long, conv_paths.hpp)
-    size_t es0 = ipa_dtype_size(dtype);
-    if (sepconv_long(es0, nky, nkx)) {
-      IPA_REQUIRE(ctx, d_src != d_dst, "sepconv2d cannot run in place");
-      if (nky == 0 || nkx == 0) {
-        const double* k = nky ? ky : kx;
-        return ipa_conv2d_dev(ctx, d_src, dtype, h, w, src_pitch, k, nky ? nky : 1, nkx ? nkx : 1,
-                              nullptr, 0, d_dst, dst_pitch, n_frames, src_frame_stride,
-                              dst_frame_stride, border_x, border_y, border_value);
-      }
-      void* tmp = nullptr;
-      IPA_HIP(ctx, hipSetDevice(ctx->device));
-      IPA_HIP(ctx, hipMalloc(&tmp, (size_t)n_frames * h * w * es0));
-      int rc = ipa_conv2d_dev(ctx, d_src, dtype, h, w, src_pitch, ky, nky, 1, nullptr, 0, tmp, w,
-                              n_frames, src_frame_stride, (long)h * w, border_x, border_y,
-                              border_value);
-      if (!rc)
-        rc = ipa_conv2d_dev(ctx, tmp, dtype, h, w, w, kx, 1, nkx, nullptr, 0, d_dst, dst_pitch,
-                            n_frames, (long)h * w, dst_frame_stride, border_x, border_y,
-                            border_value);
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipFree(tmp);
-      return rc;
-    }
-  }
-  IPA_REQUIRE(ctx, (nky == 0 || (nky & 1)) && (nkx == 0 || (nkx & 1)), "tap counts must be odd");
+  // (short kernels only: long ones go to the generic kernel, even tap counts included - sepconv_taps_ok)
+  IPA_REQUIRE(ctx, sepconv_taps_ok(ipa_dtype_size(dtype), nky, nkx), "tap counts must be odd");
   IPA_REQUIRE(ctx, src_pitch >= w && dst_pitch >= w, "pitch smaller than width");
   IPA_REQUIRE(ctx, n_frames >= 1 && n_frames <= 65535, "n_frames must be in [1,65535]");
   IPA_REQUIRE(ctx, d_src != d_dst, "sepconv2d cannot run in place");
@@ -557,58 +581,41 @@ int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, 
   if (rc) return rc;
   if (dtype != IPA_F32 && dtype != IPA_F64)
     IPA_UNSUPPORTED(ctx, "sepconv2d supports float32/float64 images (got dtype %d)", dtype);
-  size_t es = ipa_dtype_size(dtype);
-  if (sepconv_wave(dtype, nky, nkx)) {
-    // float32, equal short tap counts: the wave-marching separable kernel (wave_sep.hip)
-    WaveParams wp;
-    wp.dst = (char*)d_dst; wp.dst_frame_elems = dst_frame_stride;
-    wp.dh = h; wp.dw = w; wp.dpitch = dst_pitch;
-    wp.cbx = border_x; wp.cby = border_y;
-    wp.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
-    LoadRowSrc src;
-    src.base = (const float*)d_src; src.frame_elems = src_frame_stride; src.pitch = src_pitch;
-    src.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
-    src.cval = (float)border_value;
-    IPA_HIP(ctx, hipSetDevice(ctx->device));
-    if (ipa_wave_sep_launch(ctx, wp, src, ky, nky, kx, nkx, n_frames, (float)border_value) == 0) {
-      IPA_HIP(ctx, hipGetLastError());
-      return IPA_OK;
-    }
-  }
-  SepParams p;
-  p.src = (const char*)d_src; p.dst = (char*)d_dst;
-  p.src_frame_elems = src_frame_stride; p.dst_frame_elems = dst_frame_stride;
-  p.h = h; p.w = w; p.spitch = src_pitch; p.dpitch = dst_pitch;
-  p.bx = border_x; p.by = border_y; p.cval = border_value;
-  p.tiles_x = (unsigned)((w + kTileW - 1) / kTileW);
-  p.tiles = p.tiles_x * (unsigned)((h + kTileH - 1) / kTileH);
-  p.nky = nky; p.nkx = nkx; p.hy = nky / 2; p.hx = nkx / 2;
-  p.hxa = ((p.hx + 3) / 4) * 4;
-  p.vec_in = aligned_rows(d_src, src_pitch, src_frame_stride, n_frames, es, IPA_VEC_ALIGN);
-  p.vec_out = aligned_rows(d_dst, dst_pitch, dst_frame_stride, n_frames, es, IPA_VEC_ALIGN);
-  size_t lds = sepconv_lds(es, nky, nkx);
-  IPA_REQUIRE(ctx, lds <= 160 * 1024, "separable kernel too large for LDS");
-  dim3 grid(p.tiles, (unsigned)n_frames), block(32, 8);
+  const int path = sepconv2d_path(dtype, nky, nkx);   // the one decision (conv_paths.hpp)
+  IPA_REQUIRE(ctx, path != kSepRefused, "kernel too large (%d + %d taps)", nky, nkx);
+  const Frames f = frames_of(d_src, d_dst, dtype, h, w, src_pitch, dst_pitch, n_frames, src_frame_stride,
+                             dst_frame_stride, border_x, border_y, border_value);
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (dtype == IPA_F32) {
-    SepWeights<float> sw;
-    for (int i = 0; i < nky; i++) sw.ky[i] = (float)ky[i];
-    for (int i = 0; i < nkx; i++) sw.kx[i] = (float)kx[i];
-    if (lds > kSepLdsOptIn)
-      IPA_HIP(ctx, hipFuncSetAttribute((const void*)sepconv_kernel<float>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((sepconv_kernel<float>), grid, block, lds, ctx->stream, p, sw);
-  } else {
-    SepWeights<double> sw;
-    for (int i = 0; i < nky; i++) sw.ky[i] = ky[i];
-    for (int i = 0; i < nkx; i++) sw.kx[i] = kx[i];
-    if (lds > kSepLdsOptIn)
-      IPA_HIP(ctx, hipFuncSetAttribute((const void*)sepconv_kernel<double>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((sepconv_kernel<double>), grid, block, lds, ctx->stream, p, sw);
+  switch (path) {
+    case kSepWave: {
+      // float32, equal short tap counts: the wave-marching separable kernel (wave_sep.hip)
+      WaveParams wp;
+      LoadRowSrc src;
+      wave_rows(f, wp, src);
+      return ipa_wave_sep_launch(ctx, wp, src, ky, kx, nky, n_frames);
+    }
+    case kSepLds:
+    case kSepLdsBig: return sep_lds_launch(ctx, f, dtype, ky, nky, kx, nkx, path == kSepLdsBig);
+    // long kernels (e.g. sigma = 11 -> 89 taps, filters/standardDeviation.py:23) do not fit the kernarg table / LDS
+    // planes: the generic correlation, axis by axis
+    case kSepOneGeneric:
+      return ipa_conv2d_dev(ctx, d_src, dtype, h, w, src_pitch, nky ? ky : kx, nky ? nky : 1, nkx ? nkx : 1, nullptr,
+                            0, d_dst, dst_pitch, n_frames, src_frame_stride, dst_frame_stride, border_x, border_y,
+                            border_value);
+    default: break;   // kSepTwoGeneric
   }
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  // two launches with the intermediate (rounded to the image dtype, like scipy) in a temporary device buffer; every
+  // argument has been checked by now, so its size is that of n_frames in [1, 65535] frames
+  void* tmp = nullptr;
+  IPA_HIP(ctx, hipMalloc(&tmp, (size_t)n_frames * h * w * ipa_dtype_size(dtype)));
+  rc = ipa_conv2d_dev(ctx, d_src, dtype, h, w, src_pitch, ky, nky, 1, nullptr, 0, tmp, w, n_frames, src_frame_stride,
+                      (long)h * w, border_x, border_y, border_value);
+  if (!rc)
+    rc = ipa_conv2d_dev(ctx, tmp, dtype, h, w, w, kx, 1, nkx, nullptr, 0, d_dst, dst_pitch, n_frames, (long)h * w,
+                        dst_frame_stride, border_x, border_y, border_value);
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(tmp);
+  return rc;
 }
 
 int ipa_extend_array_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, long src_pitch,
@@ -623,32 +630,12 @@ int ipa_extend_array_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int 
   if (rc) return rc;
   rc = check_border(ctx, modey);
   if (rc) return rc;
+  IPA_REQUIRE(ctx, known_dtype(dtype), "unknown dtype %d", dtype);
   dim3 grid((w + 2 * px + 63) / 64, (h + 2 * py + 3) / 4), block(64, 4);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  switch (dtype) {
-    case IPA_U8:
-      hipLaunchKernelGGL((extend_kernel<uint8_t>), grid, block, 0, ctx->stream,
-                         (const uint8_t*)d_src, h, w, src_pitch, px, py, modex, modey,
-                         (uint8_t*)d_dst, dst_pitch);
-      break;
-    case IPA_U16:
-      hipLaunchKernelGGL((extend_kernel<uint16_t>), grid, block, 0, ctx->stream,
-                         (const uint16_t*)d_src, h, w, src_pitch, px, py, modex, modey,
-                         (uint16_t*)d_dst, dst_pitch);
-      break;
-    case IPA_F32:
-      hipLaunchKernelGGL((extend_kernel<float>), grid, block, 0, ctx->stream, (const float*)d_src,
-                         h, w, src_pitch, px, py, modex, modey, (float*)d_dst, dst_pitch);
-      break;
-    case IPA_F64:
-      hipLaunchKernelGGL((extend_kernel<double>), grid, block, 0, ctx->stream,
-                         (const double*)d_src, h, w, src_pitch, px, py, modex, modey,
-                         (double*)d_dst, dst_pitch);
-      break;
-    default: IPA_REQUIRE(ctx, false, "unknown dtype %d", dtype);
-  }
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  return by_dtype(dtype, [&](auto t) {
+    return launch(ctx, extend_kernel<decltype(t)>, grid, block, 0, d_src, h, w, src_pitch, px, py, modex, modey, d_dst,
+                  dst_pitch);
+  });
 }
 
 int ipa_deinterleave_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, int channels,
@@ -678,35 +665,19 @@ int ipa_conv_path(int op, int dtype, int k0, int k1, int flags) {
 int ipa_conv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const double* kernel,
                int kh, int kw, const uint8_t* mask, void* dst, int n_frames, int border_x,
                int border_y, double border_value) {
-  if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, src && dst && h > 0 && w > 0 && n_frames >= 1, "bad arguments");
-  size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  const size_t ib = (size_t)h * w * es * n_frames, mb = mask ? (size_t)h * w : 0;
-  char* d[3];   // in, out, mask (null without one)
-  int rc = ipa_stage_in(ctx, {{src, ib}, {nullptr, ib}, {mask, mb}}, d);
-  if (rc) return rc;
-  rc = ipa_conv2d_dev(ctx, d[0], dtype, h, w, w, kernel, kh, kw, (const uint8_t*)d[2], w, d[1], w, n_frames,
-                      (long)h * w, (long)h * w, border_x, border_y, border_value);
-  if (rc) return rc;
-  return ipa_stage_out(ctx, {{dst, d[1], ib}});
+  return staged(ctx, src, dtype, h, w, n_frames, mask, dst, [&](const char* in, char* out, const uint8_t* m) {
+    return ipa_conv2d_dev(ctx, in, dtype, h, w, w, kernel, kh, kw, m, w, out, w, n_frames, (long)h * w, (long)h * w,
+                          border_x, border_y, border_value);
+  });
 }
 
 int ipa_sepconv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const double* ky,
                   int nky, const double* kx, int nkx, void* dst, int n_frames, int border_y,
                   int border_x, double border_value) {
-  if (!ctx) return IPA_ERR_BAD_ARG;
-  IPA_REQUIRE(ctx, src && dst && h > 0 && w > 0 && n_frames >= 1, "bad arguments");
-  size_t es = ipa_dtype_size(dtype);
-  IPA_REQUIRE(ctx, es, "unknown dtype");
-  const size_t ib = (size_t)h * w * es * n_frames;
-  char* d[2];   // in, out
-  int rc = ipa_stage_in(ctx, {{src, ib}, {nullptr, ib}}, d);
-  if (rc) return rc;
-  rc = ipa_sepconv2d_dev(ctx, d[0], dtype, h, w, w, ky, nky, kx, nkx, d[1], w, n_frames,
-                         (long)h * w, (long)h * w, border_y, border_x, border_value);
-  if (rc) return rc;
-  return ipa_stage_out(ctx, {{dst, d[1], ib}});
+  return staged(ctx, src, dtype, h, w, n_frames, nullptr, dst, [&](const char* in, char* out, const uint8_t*) {
+    return ipa_sepconv2d_dev(ctx, in, dtype, h, w, w, ky, nky, kx, nkx, out, w, n_frames, (long)h * w, (long)h * w,
+                             border_y, border_x, border_value);
+  });
 }
 
 }  // extern "C"

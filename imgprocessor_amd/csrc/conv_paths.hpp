@@ -47,15 +47,21 @@ static inline bool sepconv_long(size_t esize, int nky, int nkx) {
 static inline bool sepconv_wave(int dtype, int nky, int nkx) {
   return dtype == IPA_F32 && nky == nkx && (nky == 3 || nky == 5 || nky == 7 || nky == 9);
 }
+// An even tap count is refused only where the kernel is short: long ones go to the generic kernel,
+// which centres at k / 2 like scipy.  (esize of the image's dtype whatever it is, 0 if unknown: the
+// launcher refuses short even taps before it looks at the dtype.)
+static inline bool sepconv_taps_ok(size_t esize, int nky, int nkx) {
+  return sepconv_long(esize, nky, nkx) || ((nky == 0 || (nky & 1)) && (nkx == 0 || (nkx & 1)));
+}
 // 1 = marching separable wave, 2 = LDS kernel within 64 KiB, 3 = LDS kernel with the dynamic-LDS
 // opt-in, 4 = two launches of the generic kernel through a temporary, 5 = one launch of the
-// generic kernel (a long kernel on one axis only).  In the launcher's own order: long kernels
-// leave BEFORE the odd-tap check, so an even tap count is refused only where it is short.
+// generic kernel (a long kernel on one axis only).  The launcher switches on this value.
 enum { kSepRefused = 0, kSepWave = 1, kSepLds = 2, kSepLdsBig = 3, kSepTwoGeneric = 4,
        kSepOneGeneric = 5 };
 static inline int sepconv2d_path(int dtype, int nky, int nkx) {
   if (!conv_float(dtype) || nky < 0 || nkx < 0) return kSepRefused;
   const size_t es = dtype == IPA_F32 ? 4 : 8;
+  if (!sepconv_taps_ok(es, nky, nkx)) return kSepRefused;
   if (sepconv_long(es, nky, nkx)) {
     if (nky == 0 || nkx == 0)
       return conv2d_path(dtype, nky ? nky : 1, nkx ? nkx : 1, false, true) == kConvGeneric
@@ -64,7 +70,6 @@ static inline int sepconv2d_path(int dtype, int nky, int nkx) {
                    conv2d_path(dtype, 1, nkx, false, true) == kConvGeneric
                ? kSepTwoGeneric : kSepRefused;
   }
-  if ((nky && !(nky & 1)) || (nkx && !(nkx & 1))) return kSepRefused;
   if (sepconv_wave(dtype, nky, nkx)) return kSepWave;
   return sepconv_lds(es, nky, nkx) <= kSepLdsOptIn ? kSepLds : kSepLdsBig;
 }

@@ -1,8 +1,8 @@
 // frame_args.hpp — what the eight calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
-// ovs.hip, poly.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks, the
-// known element types and the dispatch on them, and the checks and grid of the 64 x 4 tiles.  Device side, for
-// the streaming per-pixel kernels of dark / flat / tss / ovs: a lane's pixel on that tile grid and vectors of
-// adjacent pixels.  launch.hpp makes the typed launch.
+// ovs.hip, poly.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
+// and the checks and grid of the 64 x 4 tiles.  Device side, for the streaming per-pixel kernels of dark / flat / tss /
+// ovs: a lane's pixel on that tile grid and vectors of adjacent pixels.  launch.hpp holds the known element types, the
+// dispatch on them and the typed launch.
 #pragma once
 #include "common.hpp"
 
@@ -21,10 +21,6 @@ template <typename T, int PX>
 struct alignas(sizeof(T) * PX) PxVec {
   T v[PX];
 };
-
-inline bool known_dtype(int dtype) {
-  return dtype == IPA_U8 || dtype == IPA_U16 || dtype == IPA_F32 || dtype == IPA_F64;
-}
 
 struct Span {
   const void* p;
@@ -47,17 +43,6 @@ bool written_overlaps(const Span (&s)[N], int k) {
     for (int j = 0; j < N; j++)
       if (j != i && overlap(s[i], s[j])) return true;
   return false;
-}
-
-// f(T{}) for the element type of `dtype`; the caller has refused unknown dtypes
-template <typename F>
-int by_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case IPA_U8: return f((unsigned char)0);
-    case IPA_U16: return f((unsigned short)0);
-    case IPA_F32: return f(float{});
-    default: return f(double{});
-  }
 }
 
 // the checks every call shares; *tiles_x and *grid for the 64 x 4 tiles

@@ -12,9 +12,10 @@
 
 using namespace ipa;
 
-void ipa_fused_sep_launch_a(ipa_ctx*, const FusedCall&, const FusedSep&);  // 3, 5 taps
-void ipa_fused_sep_launch_b(ipa_ctx*, const FusedCall&, const FusedSep&);  // 7, 9 taps
-void ipa_fused_sep_launch_c(ipa_ctx*, const FusedCall&, const FusedSep&);  // 1 tap: the remap alone
+// (these three: the status of their launches)
+int ipa_fused_sep_launch_a(ipa_ctx*, const FusedCall&, const FusedSep&);  // 3, 5 taps
+int ipa_fused_sep_launch_b(ipa_ctx*, const FusedCall&, const FusedSep&);  // 7, 9 taps
+int ipa_fused_sep_launch_c(ipa_ctx*, const FusedCall&, const FusedSep&);  // 1 tap: the remap alone
 int ipa_fused_sep_launch_c16(ipa_ctx*, const FusedCall&);  // ... uint16 into uint16 (cv2's 16U arithmetic); 1 = not covered
 int ipa_fused_sep_launch_c8(ipa_ctx*, const FusedCall&);   // ... uint8 into uint8 (cv2's 8U fixed point); 1 = not covered
 
@@ -222,11 +223,8 @@ static int fused_sep_common(ipa_ctx* ctx, const ChainArgs& a, const ChainCoords&
   if ((rc = fused_fill(ctx, f, a))) return rc;
   FusedSep q{ky, kx, nky, 0.0f};
   IPA_HIP(ctx, hipSetDevice(ctx->device));
-  if (nky == 1) ipa_fused_sep_launch_c(ctx, f, q);
-  else if (nky <= 5) ipa_fused_sep_launch_a(ctx, f, q);
-  else ipa_fused_sep_launch_b(ctx, f, q);
-  IPA_HIP(ctx, hipGetLastError());
-  return IPA_OK;
+  if (nky == 1) return ipa_fused_sep_launch_c(ctx, f, q);
+  return nky <= 5 ? ipa_fused_sep_launch_a(ctx, f, q) : ipa_fused_sep_launch_b(ctx, f, q);
 }
 
 // A homography whose output rows drift across source rows (a rotation of a few degrees) is where
@@ -325,8 +323,7 @@ int ipa_strip_remap_int(ipa_ctx* ctx, int dtype, const void* d_src, int sh, int 
   f.cval = r > 0 ? (r < top ? r : top) : 0;
   IPA_HIP(ctx, hipSetDevice(ctx->device));
   rc = dtype == IPA_U16 ? ipa_fused_sep_launch_c16(ctx, f) : ipa_fused_sep_launch_c8(ctx, f);
-  if (rc) return rc;
-  IPA_HIP(ctx, hipGetLastError());
+  if (rc) return rc;   // (1: not covered, or the status of a launch)
   ctx->strip_remaps++;
   ctx->remap_path |= IPA_REMAP_PATH_STRIP_INT;
   return IPA_OK;

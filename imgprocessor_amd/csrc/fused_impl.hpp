@@ -90,36 +90,34 @@ static inline SharedPlan fused_plan(const ipa_ctx* ctx, bool capable, const Fuse
 
 // What every batch of a chain goes through before its launch (Capable: the kernel's trait, shared_capable / sep_shared):
 // the plan; a homography's coordinates stored once; a split plan's head and tail.  launch(call, coordinates, plan) then
-// launches ONE kernel over the frames of `call`.
+// launches ONE kernel over the frames of `call` and returns its status, which is what this returns.
 // Homography batches on the shared-record loop (knob stored_coords: from that many frames): its double coordinates (two
 // fused-multiply-add chains and a division per pixel) are evaluated ONCE per (matrix, geometry) into the plan buffer
 // (stored_coords.hpp) and the record producers read them as a table - the C3 chain spent a third of its time evaluating
 // them once per four frames.
 template <typename ST, int INTERP, int K, template <typename, int> class Capable, typename Coord, typename Launch>
-static void fused_batch(ipa_ctx* ctx, const FusedCall& f, const Coord& c, const Launch& launch) {
+static int fused_batch(ipa_ctx* ctx, const FusedCall& f, const Coord& c, const Launch& launch) {
   constexpr bool capable = Capable<SampleRowSrc<ST, INTERP, Coord>, K>::value;
   FusedCall part[2];
   const SharedPlan plan = fused_plan(ctx, capable, f, part);
   if constexpr (std::is_same<Coord, HomographyCoord>::value && capable) {
     if (ctx->tune.stored_coords > 0 && f.n_frames >= ctx->tune.stored_coords && plan != kPerFrameLoop) {
       StoredCoord<double> sc;
-      if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0) {
-        fused_batch<ST, INTERP, K, Capable>(ctx, f, sc, launch);
-        return;
-      }
+      if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0)
+        return fused_batch<ST, INTERP, K, Capable>(ctx, f, sc, launch);
     }
   }
   if (plan == kSharedSplit) {
-    fused_batch<ST, INTERP, K, Capable>(ctx, part[0], c, launch);
-    fused_batch<ST, INTERP, K, Capable>(ctx, part[1], c, launch);
-    return;
+    const int rc = fused_batch<ST, INTERP, K, Capable>(ctx, part[0], c, launch);
+    return rc ? rc : fused_batch<ST, INTERP, K, Capable>(ctx, part[1], c, launch);
   }
-  launch(f, c, plan);
+  return launch(f, c, plan);
 }
 
 template <typename ST, int INTERP, typename Coord, int K>
 static void fused_launch_one(ipa_ctx* ctx, const FusedCall& call, const Coord& coord) {
-  fused_batch<ST, INTERP, K, shared_capable>(ctx, call, coord, [ctx](const FusedCall& f, const auto& c, SharedPlan plan) {
+  // (the dense chain is as it was: fused.hip checks hipGetLastError after its launchers)
+  (void)fused_batch<ST, INTERP, K, shared_capable>(ctx, call, coord, [ctx](const FusedCall& f, const auto& c, SharedPlan plan) {
     using Src = SampleRowSrc<ST, INTERP, std::decay_t<decltype(c)>>;
     Weights<float, K * K> w;
     for (int i = 0; i < K * K; i++) w.w[i] = (float)f.kernel[i];
@@ -137,6 +135,7 @@ static void fused_launch_one(ipa_ctx* ctx, const FusedCall& call, const Coord& c
                           coord_is_table<typename Src::coord_type>::value || shared_capable<Src, K>::value, false, K);
     dim3 block(64 * IPA_WPB);
     hipLaunchKernelGGL((wave_stencil_kernel<Src, K>), grid, block, 0, ctx->stream, p, s, w);
+    return IPA_OK;
   });
 }
 
@@ -180,7 +179,7 @@ template <int K> static int fused_launch_k(ipa_ctx* ctx, const FusedCall& f) {
 int IPA_CAT(ipa_fused_launch_k, IPA_FUSED_K)(ipa_ctx* ctx, const ipa::FusedCall& f) {
   return ipa::fused_launch_k<IPA_FUSED_K>(ctx, f);
 }
-// the plain float32 filter on the same skeleton (rows straight from memory)
+// the plain float32 filter on the same skeleton (rows straight from memory; declared in wave_stencil.hpp)
 int IPA_CAT(ipa_wave_conv_launch_k, IPA_FUSED_K)(ipa_ctx* ctx, const ipa::WaveParams& p0,
                                                  const ipa::LoadRowSrc& src, const double* kernel,
                                                  int n_frames) {
@@ -193,6 +192,7 @@ int IPA_CAT(ipa_wave_conv_launch_k, IPA_FUSED_K)(ipa_ctx* ctx, const ipa::WavePa
               pipe_capable<LoadRowSrc, K>::value && IPA_PIPE ? 1 : 0);
   dim3 grid = wave_grid(ctx, p, n_frames, IPA_WPB, true, false, true), block(64 * IPA_WPB);
   hipLaunchKernelGGL((wave_stencil_kernel<LoadRowSrc, K>), grid, block, 0, ctx->stream, p, src, w);
+  IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
 }
 #endif

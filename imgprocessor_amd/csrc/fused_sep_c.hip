@@ -2,13 +2,14 @@
 // fused_sep_impl.hpp, wave_sep.hpp::sep_geom<1>) - the standalone bilinear remap of frame batches (knob strip_remap)
 #include "fused_sep_impl.hpp"
 
-void ipa_fused_sep_launch_c(ipa_ctx* ctx, const ipa::FusedCall& f, const ipa::FusedSep& q) {
-  ipa::fused_sep_k<1>(ctx, f, q);
+int ipa_fused_sep_launch_c(ipa_ctx* ctx, const ipa::FusedCall& f, const ipa::FusedSep& q) {
+  return ipa::fused_sep_k<1>(ctx, f, q);
 }
 
 // integer frames into their own type with cv2's arithmetic (wave_pipe.hpp CV16: 16U float weights / 8U fixed point): maps.
 // The kernel writes such results on the shared-record loop alone, rim strips included: returns 1 - nothing launched - unless
-// the plan and wave_grid put every strip of every launch (the whole batch, or its head and tail) on that loop.
+// the plan and wave_grid put every strip of every launch (the whole batch, or its head and tail) on that loop; else the
+// status of the launches.
 template <typename T> static int strip_remap_int_launch(ipa_ctx* ctx, const ipa::FusedCall& f) {
   using namespace ipa;
   using Src = SampleRowSrc<T, kLinear, MapCoord>;
@@ -29,9 +30,10 @@ template <typename T> static int strip_remap_int_launch(ipa_ctx* ctx, const ipa:
   const double one = 1.0;
   for (int i = 0; i < parts; i++) {
     s.src = part[i].src;   // (per part)
-    launch_sep<Src, 1, T>(ctx, part[i].p, s, &one, &one, part[i].n_frames, 0.f);
+    const int rc = launch_sep<Src, 1, T>(ctx, part[i].p, s, &one, &one, part[i].n_frames, 0.f);
+    if (rc) return rc;
   }
-  return 0;
+  return IPA_OK;
 }
 int ipa_fused_sep_launch_c16(ipa_ctx* ctx, const ipa::FusedCall& f) { return strip_remap_int_launch<uint16_t>(ctx, f); }
 int ipa_fused_sep_launch_c8(ipa_ctx* ctx, const ipa::FusedCall& f) { return strip_remap_int_launch<uint8_t>(ctx, f); }

@@ -1,12 +1,15 @@
-// launch.hpp — how the secondary entry points (stencils*.hip, interp_more.hip, idw.hip, resize.hip,
-// nan_to_zero) get from run-time arguments to ONE typed kernel launch.  Host code, no state:
+// launch.hpp — how the entry points (stencils*.hip, interp_more.hip, idw.hip, resize.hip, nan_to_zero, the
+// calibration units, conv.hip) get from run-time arguments to ONE typed kernel launch.  Host code, no state:
 //   by_float(dtype, f)       f(float{}) or f(double{}); the caller has refused other dtypes
+//   by_dtype(dtype, f)       the same over the four element types of known_dtype()
 //   pick<Vs...>(v, f)        f(std::integral_constant<., V>{}) for the listed V equal to v,
 //                            kNotCovered when there is none
 //   pick_or_last<Vs...>      the same with the last listed value as the fallback
 //   launch(ctx, kernel, ...) on ctx's device and stream, every argument converted to the kernel's
 //                            declared parameter type; returns the status of the launch
-// The hot path (conv, remap*, fused*, wave_*, tile_warp*) routes its launches itself.
+// conv.hip launches its own kernels through launch().  The wave launchers it routes to (wave_sep.hip, wave_conv_big.hip,
+// the tail of fused_impl.hpp) and the rest of the hot path (remap*, fused*, tile_warp*) fill their parameters while they
+// size their grids and write hipLaunchKernelGGL themselves; the wave launchers return hipGetLastError's status.
 #pragma once
 #include <type_traits>
 
@@ -23,6 +26,21 @@ static_assert(IPA_OK == 0 && IPA_ERR_BAD_ARG < 0 && IPA_ERR_UNSUPPORTED < 0 && I
 template <typename F>
 int by_float(int dtype, F&& f) {
   return dtype == IPA_F32 ? f(float{}) : f(double{});
+}
+
+inline bool known_dtype(int dtype) {
+  return dtype == IPA_U8 || dtype == IPA_U16 || dtype == IPA_F32 || dtype == IPA_F64;
+}
+
+// f(T{}) for the element type of `dtype`; the caller has refused unknown dtypes
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case IPA_U8: return f((unsigned char)0);
+    case IPA_U16: return f((unsigned short)0);
+    case IPA_F32: return f(float{});
+    default: return f(double{});
+  }
 }
 
 template <auto... Vs, typename V, typename F>

@@ -17,6 +17,7 @@ static int launch_wave_conv_big(ipa_ctx* ctx, const WaveParams& p0, const LoadRo
   wave_strips(ctx, a.p, wave_geom<K>::OW, n_frames, K, true, 0);
   dim3 grid = wave_grid(ctx, a.p, n_frames, IPA_WPB, true, false, true), block(64 * IPA_WPB);
   hipLaunchKernelGGL((wave_stencil_big_kernel<LoadRowSrc, K>), grid, block, 0, ctx->stream, a);
+  IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
 }
 

@@ -1,17 +1,14 @@
 // wave_sep.hip - the plain separable filter on the wave-marching skeleton (wave_sep.hpp)
+#include "launch.hpp"
 #include "wave_sep.hpp"
 
-// returns 1 when the shape is not covered (caller falls back to the LDS kernel)
-int ipa_wave_sep_launch(ipa_ctx* ctx, const ipa::WaveParams& p, const ipa::LoadRowSrc& src,
-                        const double* ky, int nky, const double* kx, int nkx, int n_frames,
-                        float xcval) {
+int ipa_wave_sep_launch(ipa_ctx* ctx, const ipa::WaveParams& p, const ipa::LoadRowSrc& src, const double* ky,
+                        const double* kx, int taps, int n_frames) {
   using namespace ipa;
-  if (nky != nkx) return 1;
-  switch (nky) {
-    case 3: launch_sep<LoadRowSrc, 3>(ctx, p, src, ky, kx, n_frames, xcval); return 0;
-    case 5: launch_sep<LoadRowSrc, 5>(ctx, p, src, ky, kx, n_frames, xcval); return 0;
-    case 7: launch_sep<LoadRowSrc, 7>(ctx, p, src, ky, kx, n_frames, xcval); return 0;
-    case 9: launch_sep<LoadRowSrc, 9>(ctx, p, src, ky, kx, n_frames, xcval); return 0;
-  }
-  return 1;
+  // (src.cval: the constant x border of the intermediate is the filter's own border value)
+  const int rc = pick<3, 5, 7, 9>(taps, [&](auto K) {
+    return launch_sep<LoadRowSrc, decltype(K)::value>(ctx, p, src, ky, kx, n_frames, src.cval);
+  });
+  IPA_REQUIRE(ctx, rc != kNotCovered, "internal error: no separable wave kernel for %d taps", taps);
+  return rc;
 }

@@ -412,9 +412,10 @@ template <typename Src, int K> static dim3 sep_grid(ipa_ctx* ctx, WaveParams& p,
   return wave_grid(ctx, p, n_frames, 4, true, sep_shares_maps<Src>::value, std::is_same<Src, LoadRowSrc>::value, -K);
 }
 
+// -> the status of the launch
 template <typename Src, int K, typename DT = float>
-static void launch_sep(ipa_ctx* ctx, WaveParams p, const Src& src, const double* ky,
-                       const double* kx, int n_frames, float xcval) {
+static int launch_sep(ipa_ctx* ctx, WaveParams p, const Src& src, const double* ky,
+                      const double* kx, int n_frames, float xcval) {
   SepTaps<K> w;
   for (int i = 0; i < K; i++) {
     w.ky[i] = (float)ky[i];
@@ -422,6 +423,8 @@ static void launch_sep(ipa_ctx* ctx, WaveParams p, const Src& src, const double*
   }
   const dim3 grid = sep_grid<Src, K>(ctx, p, n_frames);   // (fills p: before the launch takes it)
   hipLaunchKernelGGL((wave_sep_kernel<Src, K, DT>), grid, dim3(256), 0, ctx->stream, p, src, w, xcval);
+  IPA_HIP(ctx, hipGetLastError());
+  return IPA_OK;
 }
 
 }  // namespace ipa

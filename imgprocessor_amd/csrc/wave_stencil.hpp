@@ -1028,3 +1028,15 @@ static inline void wave_strips(const ipa_ctx* ctx, WaveParams& p, int ow, int n_
 }
 
 }  // namespace ipa
+
+// The plain-row launchers conv.hip routes to; each returns the status of its launch.
+// float32 K x K filter (one translation unit per K: fused_k3 / k5 / k7.hip through the tail of fused_impl.hpp,
+// wave_conv_big.hip for 9 and 11)
+int ipa_wave_conv_launch_k3(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* kernel, int n_frames);
+int ipa_wave_conv_launch_k5(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* kernel, int n_frames);
+int ipa_wave_conv_launch_k7(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* kernel, int n_frames);
+int ipa_wave_conv_launch_k9(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* kernel, int n_frames);
+int ipa_wave_conv_launch_k11(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* kernel, int n_frames);
+// float32 separable filter of `taps` = 3, 5, 7, 9 taps on both axes (wave_sep.hip: what sepconv2d_path calls kSepWave)
+int ipa_wave_sep_launch(ipa_ctx*, const ipa::WaveParams&, const ipa::LoadRowSrc&, const double* ky, const double* kx,
+                        int taps, int n_frames);

@@ -271,8 +271,9 @@ int ipa_conv2d(ipa_ctx* ctx, const void* src, int dtype, int h, int w, const dou
  * camera/flatField/flatField.py:47.  Single pass over HBM.
  * Tap counts: up to 63 per axis (and two LDS planes within 150 KiB) run in the single-pass
  * kernels, which are centred on an odd count only - an EVEN count there is IPA_ERR_BAD_ARG.
- * Longer kernels run axis by axis on the generic correlation BEFORE that check, so an even
- * count of 64 taps or more is accepted and centred on tap n / 2 like scipy's correlate1d
+ * Longer kernels run axis by axis on the generic correlation and that check leaves them out
+ * (sepconv_taps_ok, csrc/conv_paths.hpp), so an even count of 64 taps or more is accepted and
+ * centred on tap n / 2 like scipy's correlate1d
  * (tests/test_gpu_conv_paths.py pins both).  The inconsistency is known and kept: callers that
  * need even kernels of any length have ipa_conv2d_dev with kh or kw = 1. */
 int ipa_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int dtype, int h, int w, long src_pitch,

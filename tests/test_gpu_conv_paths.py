@@ -342,6 +342,87 @@ def test_refusals(ctx):
     assert np.array_equal(src.get(), img)
 
 
+# (name, entry point, the arguments that differ from a good call, status).  The statuses are those of the checks
+# in the order the entry points make them: every BAD_ARG check before the dtype's UNSUPPORTED, short even tap
+# counts before the dtype, long ones never.  `inplace`: the destination is the source.
+U8 = np.uint8
+REFUSAL_ORDER = (
+    ('conv2d-null-kernel', 'conv', dict(k=None), 'ERR_BAD_ARG'),
+    ('conv2d-kh0', 'conv', dict(kh=0), 'ERR_BAD_ARG'),
+    ('conv2d-frames0', 'conv', dict(n=0), 'ERR_BAD_ARG'),
+    ('conv2d-frames65536', 'conv', dict(n=65536), 'ERR_BAD_ARG'),
+    ('conv2d-mask-pitch', 'conv', dict(mask=True, mp=19), 'ERR_BAD_ARG'),
+    ('conv2d-u8-src-pitch', 'conv', dict(dt=U8, sp=19), 'ERR_BAD_ARG'),       # pitch before dtype
+    ('conv2d-u8-border', 'conv', dict(dt=U8, bx=-1), 'ERR_BAD_ARG'),
+    ('conv2d-u8-inplace', 'conv', dict(dt=U8, inplace=True), 'ERR_BAD_ARG'),
+    ('conv2d-257x256', 'conv', dict(k=(257, 256)), 'ERR_BAD_ARG'),            # 65 792 taps
+    ('sep-nky-1', 'sep', dict(ky=3, nky=-1), 'ERR_BAD_ARG'),
+    ('sep-null-ky', 'sep', dict(ky=None, nky=3), 'ERR_BAD_ARG'),
+    ('sep-4taps-u8', 'sep', dict(ky=4, kx=4, dt=U8), 'ERR_BAD_ARG'),          # odd taps before dtype
+    ('sep-3taps-u8-dst-pitch', 'sep', dict(dt=U8, dp=19), 'ERR_BAD_ARG'),
+    ('sep-3taps-u8', 'sep', dict(dt=U8), 'ERR_UNSUPPORTED'),
+    ('sep-64taps-u8', 'sep', dict(ky=64, kx=64, dt=U8), 'ERR_UNSUPPORTED'),
+    ('sep-64taps-inplace', 'sep', dict(ky=64, kx=64, inplace=True), 'ERR_BAD_ARG'),
+    ('sep-64taps-src-pitch', 'sep', dict(ky=64, kx=64, sp=19), 'ERR_BAD_ARG'),
+    # these two: refused before the temporary of the two generic launches is sized from n_frames
+    ('sep-64taps-frames-1', 'sep', dict(ky=64, kx=64, n=-1), 'ERR_BAD_ARG'),
+    ('sep-64taps-frames0', 'sep', dict(ky=64, kx=64, n=0), 'ERR_BAD_ARG'),
+    # ... and so before the first generic launch met the dtype: it was UNSUPPORTED while the destination's pitch
+    # was looked at by the second launch only
+    ('sep-64taps-u8-dst-pitch', 'sep', dict(ky=64, kx=64, dt=U8, dp=19), 'ERR_BAD_ARG'),
+    ('sep-65537taps', 'sep', dict(ky=65537, kx=0), 'ERR_BAD_ARG'),            # more than the generic kernel takes
+    ('sep-0taps', 'sep', dict(ky=0, kx=0), 'OK'),                             # no axis: a copy
+)
+
+
+@pytest.mark.parametrize('row', REFUSAL_ORDER, ids=[r[0] for r in REFUSAL_ORDER])
+def test_refusal_order(ctx, row):
+    """the status of every refusal whose place among the checks decides it, on the C ABI alone: a 9 x 20 float32
+    frame, FILL in the destination.  Afterwards the destination is still FILL - after the one call that succeeds,
+    without taps on either axis, the bits of the source - and the source is intact."""
+    from imgprocessor_amd import _lib, ops
+    from imgprocessor_amd.device import dtype_id
+    name, op, a, want = row
+    L, hnd = ctx._lib, ctx.handle
+    h, w = 9, 20
+    assert a.get('sp', w) in (w, w - 1) and a.get('dp', w) in (w, w - 1) and a.get('mp', w) in (w, w - 1)
+    img = cc.frame((h, w), F32)
+    src, dst = ctx.to_device(img), ctx.to_device(np.full((h, w), FILL, F32))
+    d = src if a.get('inplace') else dst
+    dt, refl = dtype_id(a.get('dt', F32)), ops.border_id('reflect')
+    n, sp, dp = a.get('n', 1), a.get('sp', w), a.get('dp', w)
+    keep = []
+
+    def ptr(v, make):
+        """null for None, else the float64 array make(v) - kept alive until the call returns"""
+        if v is None:
+            return None
+        arr, p = _dp(make(v))
+        keep.append(arr)
+        return p
+
+    if op == 'conv':
+        kshape = a.get('k', (3, 3))
+        pk = ptr(kshape, lambda s: np.full(s, 1.0 / (s[0] * s[1])))
+        kh, kw = kshape if kshape is not None else (3, 3)
+        m = ctx.to_device(np.ones((h, w), np.uint8)) if a.get('mask') else None
+        rc = L.ipa_conv2d_dev(hnd, src.ptr, dt, h, w, sp, pk, a.get('kh', kh), kw, m.ptr if m is not None else None,
+                              a.get('mp', w), d.ptr, dp, n, h * w, h * w, a.get('bx', refl), refl, 0.0)
+    else:
+        ky, kx = a.get('ky', 3), a.get('kx', 3)
+        pky, pkx = (ptr(t, lambda c: cc.taps(c) if c else np.zeros(1)) for t in (ky, kx))
+        rc = L.ipa_sepconv2d_dev(hnd, src.ptr, dt, h, w, sp, pky, a.get('nky', ky), pkx, kx, d.ptr, dp, n, h * w,
+                                 h * w, refl, refl, 0.0)
+    assert rc == getattr(_lib, want), '%s: status %d (%s)' % (
+        name, rc, (L.ipa_last_error(hnd) or b'').decode() if rc else '')
+    out = dst.get()
+    if want == 'OK':
+        assert np.array_equal(out.view(np.uint32), img.view(np.uint32)), 'no taps: not the bits of the source'
+    else:
+        assert (out == FILL).all(), 'a refused call wrote to the destination'
+    assert np.array_equal(src.get(), img)
+
+
 @pytest.mark.parametrize('nky,nkx', [(64, 0), (0, 64), (64, 3), (64, 64)])
 def test_long_even_taps_are_accepted(ctx, oracle, nky, nkx):
     """64 taps on an axis leave for the generic kernel BEFORE the odd-tap check that refuses 4:
