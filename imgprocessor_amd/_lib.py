@@ -184,6 +184,13 @@ PROTOTYPES = {
     'ipa_poly2d_eval_dev': [_vp, _dp, _i, _i, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp, _i, _i, _l, _vp, _l, _dp],
     'ipa_high_grad_dev': [_vp, _vp, _i, _i, _i, _l, _d, _i, _vp, _l, _dp],
     'ipa_clip01_dev': [_vp, _vp, _i, _i, _i, _l],
+    'ipa_spot_range_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _dp],
+    'ipa_spot_histogram_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _dp, _i, _vp],
+    'ipa_spot_mask_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _d, _vp, _l],
+    'ipa_label_dev': [_vp, _vp, _i, _i, _l, _i, _vp, _l, _ip],
+    'ipa_label_sizes_dev': [_vp, _vp, _i, _i, _l, _i, _vp],
+    'ipa_label_largest_dev': [_vp, _vp, _i, _i, _l, _i, _vp],
+    'ipa_spot_take_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _vp, _l, _i, _i, _i, _vp, _l, _vp, _l, _dp],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

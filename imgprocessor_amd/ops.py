@@ -27,6 +27,8 @@ from .ops_ovs import ovs_object, ovs_flatfield, masked_running_mean_update  # no
 # the 2-D polynomial fit family lives in ops_poly.py
 from .ops_poly import (poly2d_moments, poly2d_gram, poly2d_solve, poly2d_eval, high_grad_window,  # noqa: F401
                        high_grad_mask, clip01)
+# the spot family (histogram, Otsu, labelling) lives in ops_spot.py
+from .ops_spot import histogram, otsu_threshold, spot_mask, label, largest_component, spot_take  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -1019,6 +1019,74 @@ int ipa_high_grad_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
 /* polynomial.py:49 - np.clip(img, 0, 1, out=img): in place, NaN stays. */
 int ipa_clip01_dev(ipa_ctx* ctx, void* d_img, int dtype, int h, int w, long pitch);
 
+/* ---- flat field from spot images (csrc/spot.hip) ------------------------------------------------
+ * camera/flatField/vignettingFromSpotAverage.py ("Method B") and the primitives under it: a
+ * histogram by np.histogram's bin rule, the range skimage's threshold_otsu starts from, the eroded
+ * threshold mask, connected-component labelling, component sizes, the largest component and the
+ * copy of a spot into the sparse result.  Frames are uint8 / uint16 / float32 / float64 (another
+ * dtype: IPA_ERR_UNSUPPORTED), pitches in elements; a frame value is (double)px - bg, one IEEE
+ * subtraction, with bg = d_bg[y][x] (float64, bg_pitch) or, where d_bg is NULL, the scalar bg.
+ * h * w < 2^31.  Null pointers, an empty image and a pitch smaller than the width are
+ * IPA_ERR_BAD_ARG; nothing is written on refusal and padding is never written.  The calls that
+ * return host values synchronise the stream. */
+
+/* vignettingFromSpotAverage.py:56 (threshold_otsu's `np.all(image == first_pixel)` and the range of
+ * np.histogram) - range (HOST, 5 doubles) = {min, max, number of NaN, number of +-inf, the first
+ * pixel}; min and max are exact and skip NaN (+inf, -inf without a comparable value).
+ * Per-workgroup partials and a second small launch. */
+int ipa_spot_range_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
+                       long bg_pitch, double bg, double* range);
+
+/* vignettingFromSpotAverage.py:56 (np.histogram(image.ravel(), nbins) inside threshold_otsu) -
+ * counts (HOST, nbins) over the edges (HOST, nbins + 1, np.linspace(lo, hi, nbins + 1)), by
+ * np.histogram's rule for equal bins: the estimate k = (intp)((x - e[0]) * (nbins / (e[nbins] - e[0]))),
+ * k == nbins -> nbins - 1, then `x < e[k]` lowers k and `x >= e[k + 1]` with k != nbins - 1 raises
+ * it, so that e[k] <= x < e[k + 1] with the last bin closed.  Every frame value must be finite
+ * and lie within [e[0], e[nbins]] (ipa_spot_range_dev tells).  1 <= nbins <= 2048 (above:
+ * IPA_ERR_UNSUPPORTED).  Per-wave tables in LDS, integer adds only: the counts are exact. */
+int ipa_spot_histogram_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
+                           long bg_pitch, double bg, const double* edges, int nbins, unsigned long long* counts);
+
+/* vignettingFromSpotAverage.py:61 (minimum_filter(img > t, 3)) - d_mask (uint8 0 / 1) = the 3 x 3
+ * erosion of `frame - bg > t`; positions beyond the frame do not count (scipy's `reflect` border on
+ * a bool image), NaN > t is false.  Not in place. */
+int ipa_spot_mask_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
+                      long bg_pitch, double bg, double t, unsigned char* d_mask, long mask_pitch);
+
+/* vignettingFromSpotAverage.py:61 (skimage.measure.label(., background=0, return_num=True); also
+ * scipy.ndimage.label) - d_labels (int32): 0 where d_mask (uint8) is 0, otherwise the number of the
+ * pixel's connected component, 1 .. *n (HOST), numbered in the raster order of the components'
+ * first pixels.  connectivity 1: the 4 edge neighbours (scipy's default); 2: all 8 (skimage's
+ * default on images); anything else IPA_ERR_BAD_ARG.  A union-find whose roots are the smallest
+ * linear index of their component, tiles in LDS, seams by atomic minimum; 4 h w bytes of the
+ * context's workspace.  d_labels must not overlap d_mask. */
+int ipa_label_dev(ipa_ctx* ctx, const unsigned char* d_mask, int h, int w, long mask_pitch, int connectivity,
+                  int* d_labels, long label_pitch, int* n);
+
+/* vignettingFromSpotAverage.py:63 (spot_sizes) - d_sizes (DEVICE, n int64): d_sizes[i] = the number
+ * of pixels of label i + 1; labels beyond n are not counted.  Integer adds, aggregated per wave. */
+int ipa_label_sizes_dev(ipa_ctx* ctx, const int* d_labels, int h, int w, long label_pitch, int n,
+                        long long* d_sizes);
+
+/* vignettingFromSpotAverage.py:66 and :72 (np.argmax(spot_sizes) + 1; the sums under
+ * center_of_mass) - result (HOST, 4 int64) = {label, size, sum of y, sum of x} of the largest of
+ * the n components, the lowest label among equals; all 0 for n = 0.  The sums are exact integers:
+ * center_of_mass is sum / size in float64 on the host. */
+int ipa_label_largest_dev(ipa_ctx* ctx, const int* d_labels, int h, int w, long label_pitch, int n,
+                          long long* result);
+
+/* vignettingFromSpotAverage.py:72-77 (mx2; fitimg[spot] = img[spot]; mask[spot] = 1) - for the
+ * pixels p of `label` in d_labels (the spot form) or, where d_labels is NULL, of the whole rows
+ * row_a and row_b (the row form: what `img[spot]` selects once `spot` is an index pair),
+ * d_fit[p] (float64) = frame[p] - bg and d_mask[p] (uint8) = 1; every other pixel of both is left
+ * alone.  result (HOST, 3 doubles) = {maximum (NaN if a value is; -inf for none), sum, count}; the
+ * sum is added in an order the frame's size alone decides: identical bits from call to call.
+ * label >= 1; 0 <= row_a, row_b < h.  An output that overlaps anything is IPA_ERR_BAD_ARG. */
+int ipa_spot_take_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
+                      long bg_pitch, double bg, const int* d_labels, long label_pitch, int label, int row_a,
+                      int row_b, double* d_fit, long fit_pitch, unsigned char* d_mask, long mask_pitch,
+                      double* result);
+
 #ifdef __cplusplus
 }
 #endif
