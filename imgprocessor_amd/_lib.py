@@ -191,6 +191,10 @@ PROTOTYPES = {
     'ipa_label_sizes_dev': [_vp, _vp, _i, _i, _l, _i, _vp],
     'ipa_label_largest_dev': [_vp, _vp, _i, _i, _l, _i, _vp],
     'ipa_spot_take_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _d, _vp, _l, _i, _i, _i, _vp, _l, _vp, _l, _dp],
+    'ipa_cell_means_dev': [_vp, _vp, _i, _i, _i, _i, _l, _l, _vp, _i, _l, _d, _ip, _i, _ip, _i, _vp],
+    'ipa_steps_separate_dev': [_vp, _vp, _i, _i, _i, _i, _i, _ip, _d, _i, _i, _d, _vp, _vp, _vp, _ip, _dp],
+    'ipa_offset_meshgrid_dev': [_vp, _d, _d, _d, _d, _d, _d, _i, _i, _i, _vp, _vp, _l],
+    'ipa_isnan_mask_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

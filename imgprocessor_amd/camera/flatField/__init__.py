@@ -1,4 +1,5 @@
-from .vignettingFromDiscreteSteps import rescaleToGrid  # noqa: F401
+from .vignettingFromDiscreteSteps import (rescaleToGrid, vignettingFromDiscreteSteps,  # noqa: F401
+                                          positionsFromRaster, positionsFromTopLeftCorner)
 from .flatFieldFromCloseDistance import (flatFieldFromCloseDistance,  # noqa: F401
                                          flatFieldFromCloseDistance2)
 from .sensitivity import sensitivity  # noqa: F401

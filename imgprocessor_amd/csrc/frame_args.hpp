@@ -1,5 +1,5 @@
-// frame_args.hpp — what the nine calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
-// ovs.hip, poly.hip, spot.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
+// frame_args.hpp — what the ten calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
+// ovs.hip, poly.hip, spot.hip, steps.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
 // and the checks and grid of the 64 x 4 tiles.  Device side, for the streaming per-pixel kernels of dark / flat / tss /
 // ovs: a lane's pixel on that tile grid and vectors of adjacent pixels.  launch.hpp holds the known element types, the
 // dispatch on them and the typed launch.

@@ -6,3 +6,4 @@ from .interpolateCircular2dStructuredIDW import interpolateCircular2dStructuredI
 from .interpolate2dStructuredCrossAvg import interpolate2dStructuredCrossAvg  # noqa: F401
 from .interpolate2dStructuredPointSpreadIDW import interpolate2dStructuredPointSpreadIDW  # noqa: F401
 from .polyfit2d import polyfit2dGrid  # noqa: F401
+from .offsetMeshgrid import offsetMeshgrid  # noqa: F401

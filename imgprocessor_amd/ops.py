@@ -29,6 +29,8 @@ from .ops_poly import (poly2d_moments, poly2d_gram, poly2d_solve, poly2d_eval, h
                        high_grad_mask, clip01)
 # the spot family (histogram, Otsu, labelling) lives in ops_spot.py
 from .ops_spot import histogram, otsu_threshold, spot_mask, label, largest_component, spot_take  # noqa: F401
+# the discrete-steps family (cell means, the separation loop, the offset grid) lives in ops_steps.py
+from .ops_steps import cell_edges, cell_means, steps_separate, offset_meshgrid, isnan_mask  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -1087,6 +1087,62 @@ int ipa_spot_take_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
                       int row_b, double* d_fit, long fit_pitch, unsigned char* d_mask, long mask_pitch,
                       double* result);
 
+/* ---- flat field from discrete steps (csrc/steps.hip) --------------------------------------------
+ * camera/flatField/vignettingFromDiscreteSteps.py up to its post-processing: the device is imaged
+ * at known cell positions, every frame is reduced to the thresholded means of a grid of cells, and
+ * device and flat field are separated iteratively on that grid.  At most 64 frames
+ * (IPA_ERR_UNSUPPORTED above); pitches and strides in elements.  Nothing is written on refusal. */
+
+/* replaces vignettingFromDiscreteSteps.py:228-246 (array/subCell2D.py:87-107, subCell2DFnArray with
+ * the cell function of :228-234) for all n frames: cell (i, j) is rows row_edges[i] ..
+ * row_edges[i + 1] - 1 and columns col_edges[j] .. col_edges[j + 1] - 1 (HOST tables of g0 + 1 and
+ * g1 + 1 entries that do not decrease and lie within [0, h] and [0, w]: the slices of
+ * subCell2DSlices clipped to the frame).  With x = (double)frame - (double)bg (d_bg: one h x w
+ * frame of any of the four types, or NULL: x = (double)frame), count = #(x > thresh) - a NaN is no
+ * sample - and size = rows * cols, d_grid[n][i][j] (float64, dense n x g0 x g1) is NaN where
+ * size == 0 or 2 * count < size and sum(x where x > thresh) / count elsewhere.
+ * Every frame element is read once and nothing of frame size is written.  The sum's order is
+ * fixed - a lane adds up to 32 rows of its column, a fixed tree adds the columns of a cell within
+ * 256 columns, such spans are added left to right and the 32-row segments top to bottom; no
+ * atomics - so two calls give identical bits.  The partial sums live in the context's workspace:
+ * n * g0 * S * g1 of them, S = ceil(tallest cell row / 32), at most 2^24 (IPA_ERR_UNSUPPORTED
+ * above, as for w >= 2^26). */
+int ipa_cell_means_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int h, int w, long pitch,
+                       long frame_stride, const void* d_bg, int bg_dtype, long bg_pitch, double thresh,
+                       const int* row_edges, int g0, const int* col_edges, int g1, double* d_grid);
+
+/* replaces vignettingFromDiscreteSteps.py:257-281 and :316 in ONE launch of one workgroup.
+ * d_grid: float64, dense n x g0 x g1, what ipa_cell_means_dev wrote.  rects (HOST): per frame the
+ * six ints {q0, q1, qq0, qq1, l0, l1} of _DeviceAndGridSlice.iter() (:26-60): device cells
+ * [q0, q0 + l0) x [q1, q1 + l1) are grid cells [qq0, qq0 + l0) x [qq1, qq1 + l1); a rectangle that
+ * leaves the n0 x n1 device or the grid is IPA_ERR_BAD_ARG.  Every np.nanmean(axis=0) is numpy's:
+ * NaN -> 0, a sum in frame order, divided by the number of non-NaN terms (0 / 0 = NaN); the
+ * initial flat field is nanmean(grid) [- bg_value where subtract_bg] / nanmax.
+ * d_ff: float64 g0 x g1; d_avgobj: float64 n0 x n1; d_density: int32 g0 x g1, the number of
+ * non-NaN frames per cell; *iterations and *dev (HOST): the iterations run and the last RMS
+ * deviation (summed in this kernel's own fixed order; only the stop decision reads it).
+ * DEVIATION: the reference's inner loops reuse the name of its iteration counter, so max_iter
+ * never ends its loop.  Here iteration k = 1, 2, ... is the last when dev < max_dev or
+ * k > max_iter + 1 - what the reference's counter would give - so at most max_iter + 2 run; a NaN
+ * dev runs to that cap.  0 <= max_iter <= 10000 (IPA_ERR_BAD_ARG); at most 2^16 grid cells and
+ * 2^16 device cells (IPA_ERR_UNSUPPORTED).  Synchronises the stream. */
+int ipa_steps_separate_dev(ipa_ctx* ctx, const double* d_grid, int n, int g0, int g1, int n0, int n1,
+                           const int* rects, double bg_value, int subtract_bg, int max_iter, double max_dev,
+                           double* d_ff, double* d_avgobj, int* d_density, int* iterations, double* dev);
+
+/* replaces interpolate/offsetMeshgrid.py:25-27 (and the astype(np.float32) of
+ * vignettingFromDiscreteSteps.py:312): d_yy[y][x] = lin0[y], d_xx[y][x] = lin1[x] with
+ * lin[i] = i * step + start and, for an axis longer than 1, the last element = stop - np.linspace
+ * with step = (stop - start) / (len - 1) formed on the host.  dtype IPA_F64, or IPA_F32: the
+ * double rounded once. */
+int ipa_offset_meshgrid_dev(ipa_ctx* ctx, double start0, double step0, double stop0, double start1, double step1,
+                            double stop1, int h, int w, int dtype, void* d_yy, void* d_xx, long pitch);
+
+/* replaces vignettingFromDiscreteSteps.py:289 (np.isnan): d_mask (uint8) = 1 where the float32 /
+ * float64 frame is NaN, 0 elsewhere. */
+int ipa_isnan_mask_dev(ipa_ctx* ctx, const void* d_in, int dtype, int h, int w, long pitch, unsigned char* d_mask,
+                       long mask_pitch);
+
 #ifdef __cplusplus
 }
 #endif
