@@ -22,6 +22,7 @@
 #include "interp_paths.hpp"
 #include "launch.hpp"
 #include "nlf_fn.hpp"
+#include "reduce.hpp"
 
 #pragma clang fp contract(off)
 
@@ -90,21 +91,14 @@ luma_kernel(const double* __restrict__ img, int h, int w, long pitch, int tiles_
   out[(long)y * out_pitch + x] = ((p[0] * wr + p[1] * wg) + p[2] * wb) / wsum;
 }
 
-// tree over the workgroup's threads in a fixed order; MODE 0 maximum, 1 minimum (numpy's: a NaN wins)
+// an extremum and how two of them merge: MODE 0 maximum, 1 minimum (numpy's: a NaN wins)
 template <int MODE>
-__device__ inline double ext2(double a, double b) {
-  return MODE == 0 ? np_max(a, b) : np_min(a, b);
-}
+struct Ext {
+  double v;
+};
 template <int MODE>
-__device__ inline double block_ext(double v, double* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int s = kFlatThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = ext2<MODE>(lds[t], lds[t + s]);
-    __syncthreads();
-  }
-  return lds[0];
+__device__ inline Ext<MODE> merge(Ext<MODE> a, Ext<MODE> b) {
+  return {MODE == 0 ? np_max(a.v, b.v) : np_min(a.v, b.v)};
 }
 
 // The sampled grid a[::sy, ::sx] has gh x gw points.  MODE 0: a lane takes the 3 x 3 median of a
@@ -114,10 +108,9 @@ template <typename T, int MODE>
 __global__ void __launch_bounds__(kFlatThreads)
 strided_extremum_kernel(const T* __restrict__ img, long pitch, int gh, int gw, int sy, int sx,
                         double* __restrict__ part) {
-  __shared__ double lds[kFlatThreads];
+  __shared__ Ext<MODE> lds[kFlatThreads];
   const long n = (long)gh * gw;
-  const double none = MODE == 0 ? -__builtin_inf() : __builtin_inf();
-  double m = none;
+  Ext<MODE> m = {MODE == 0 ? -__builtin_inf() : __builtin_inf()};
   for (long i = (long)blockIdx.x * kFlatThreads + threadIdx.x; i < n; i += (long)gridDim.x * kFlatThreads) {
     const int gy = (int)(i / gw), gx = (int)(i - (long)gy * gw);
     double v;
@@ -136,21 +129,20 @@ strided_extremum_kernel(const T* __restrict__ img, long pitch, int gh, int gw, i
     } else {
       v = (double)img[(long)gy * sy * pitch + (long)gx * sx];
     }
-    m = ext2<MODE>(m, v);
+    m = merge(m, Ext<MODE>{v});
   }
-  m = block_ext<MODE>(m, lds);
-  if (threadIdx.x == 0) part[blockIdx.x] = m;
+  m = block_merge<kFlatThreads>(m, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = m.v;
 }
 
 // one workgroup: the partials in workgroup order -> res[0]
 template <int MODE>
 __global__ void __launch_bounds__(kFlatThreads)
 extremum_final_kernel(const double* __restrict__ part, int n_part, double* __restrict__ res) {
-  __shared__ double lds[kFlatThreads];
-  double m = MODE == 0 ? -__builtin_inf() : __builtin_inf();
-  for (int p = threadIdx.x; p < n_part; p += kFlatThreads) m = ext2<MODE>(m, part[p]);
-  m = block_ext<MODE>(m, lds);
-  if (threadIdx.x == 0) res[0] = m;
+  __shared__ Ext<MODE> lds[kFlatThreads];
+  const Ext<MODE> none = {MODE == 0 ? -__builtin_inf() : __builtin_inf()};
+  const Ext<MODE> m = merge_partials<kFlatThreads>((const Ext<MODE>*)part, n_part, none, lds);   // one double each
+  if (threadIdx.x == 0) res[0] = m.v;
 }
 
 __global__ void __launch_bounds__(kFlatThreads)
@@ -392,10 +384,9 @@ int ipa_strided_extremum_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, 
   const int gh = (h + step_y - 1) / step_y, gw = (w + step_x - 1) / step_x;
   const long blocks = ((long)gh * gw + kFlatThreads - 1) / kFlatThreads;
   const int grid = (int)(blocks < kExtMaxGrid ? blocks : kExtMaxGrid);
-  int rc = ipa_ws_reserve(ctx, (size_t)(kExtMaxGrid + 1) * 8);
+  double *part, *res;
+  int rc = stage_ws(ctx, slot(&part, grid), slot(&res, 1));
   if (rc) return rc;
-  double* part = (double*)ctx->ws;
-  double* res = part + kExtMaxGrid;
   if (mode == IPA_EXTREMUM_MEDIAN_MAX) {
     rc = launch(ctx, strided_extremum_kernel<double, 0>, dim3(grid), dim3(kFlatThreads), 0, d_img, pitch, gh, gw,
                 step_y, step_x, part);
@@ -408,9 +399,7 @@ int ipa_strided_extremum_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, 
     if (!rc) rc = launch(ctx, extremum_final_kernel<1>, dim3(1), dim3(kFlatThreads), 0, part, grid, res);
   }
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(result, res, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{result, res, sizeof(double)}});
 }
 
 int ipa_flat_scale_dev(ipa_ctx* ctx, const double* d_img, int h, int w, long pitch, const double* d_bg,

@@ -1,8 +1,10 @@
 // frame_args.hpp — what the ten calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
 // ovs.hip, poly.hip, spot.hip, steps.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
-// and the checks and grid of the 64 x 4 tiles.  Device side, for the streaming per-pixel kernels of dark / flat / tss /
-// ovs: a lane's pixel on that tile grid and vectors of adjacent pixels.  launch.hpp holds the known element types, the
-// dispatch on them and the typed launch.
+// the checks and grid of the 64 x 4 tiles, and stage_ws(): the workspace of a call as a list of typed slots over
+// ipa_stage_in (common.hpp), which ipa_stage_out answers at the call's end.  Device side, for the streaming per-pixel
+// kernels of dark / flat / tss / ovs: a lane's pixel on that tile grid and vectors of adjacent pixels.  launch.hpp holds
+// the known element types, the dispatch on them and the typed launch; reduce.hpp the workgroup reduction of the units
+// that sum a frame up (block_merge, merge_partials).
 #pragma once
 #include "common.hpp"
 
@@ -43,6 +45,28 @@ bool written_overlaps(const Span (&s)[N], int k) {
     for (int j = 0; j < N; j++)
       if (j != i && overlap(s[i], s[j])) return true;
   return false;
+}
+
+// ipa_stage_in with every slot's pointer in its own type: slot(&p, n) is n elements of *p, uploaded from `host`
+// where one is given; p is null for n == 0.
+//   Moments* part;  double* res;
+//   rc = stage_ws(ctx, slot(&part, grid), slot(&res, 5));
+template <typename T>
+struct WsSlot {
+  T** p;
+  size_t n;
+  const T* host;
+};
+template <typename T>
+WsSlot<T> slot(T** p, size_t n, const T* host = nullptr) { return {p, n, host}; }
+template <typename... T>
+int stage_ws(ipa_ctx* ctx, WsSlot<T>... s) {
+  char* d[sizeof...(T)];
+  const int rc = ipa_stage_in(ctx, {{s.host, s.n * sizeof(T)}...}, d);
+  if (rc) return rc;
+  int i = 0;
+  ((*s.p = (T*)d[i++]), ...);
+  return IPA_OK;
 }
 
 // the checks every call shares; *tiles_x and *grid for the 64 x 4 tiles

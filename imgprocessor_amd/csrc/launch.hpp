@@ -7,6 +7,8 @@
 //   pick_or_last<Vs...>      the same with the last listed value as the fallback
 //   launch(ctx, kernel, ...) on ctx's device and stream, every argument converted to the kernel's
 //                            declared parameter type; returns the status of the launch
+// The calibration units reserve their workspace and read their results back through stage_ws() (frame_args.hpp) and
+// ipa_stage_out (common.hpp), and reduce through reduce.hpp.
 // conv.hip launches its own kernels through launch().  The wave launchers it routes to (wave_sep.hip, wave_conv_big.hip,
 // the tail of fused_impl.hpp) and the rest of the hot path (remap*, fused*, tile_warp*) fill their parameters while they
 // size their grids and write hipLaunchKernelGGL themselves; the wave launchers return hipGetLastError's status.

@@ -25,6 +25,7 @@
 #include "frame_args.hpp"
 #include "launch.hpp"
 #include "nlf_fn.hpp"
+#include "reduce.hpp"
 
 #pragma clang fp contract(off)
 
@@ -88,18 +89,6 @@ __device__ inline Moments merge(const Moments& a, const Moments& b) {
   return {a.sum + b.sum, b.mn < a.mn ? b.mn : a.mn, b.mx > a.mx ? b.mx : a.mx, a.nan + b.nan};
 }
 
-// tree over the workgroup's threads in a fixed order; the result is thread 0's
-__device__ inline Moments block_merge(Moments v, Moments* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int s = kNlfThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = merge(lds[t], lds[t + s]);
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 // pass 0: sum / min / max / NaN count of the non-NaN values; pass 1: sum of (x - mean)^2 with
 // the mean of pass 0 read from res[2].  A unit is 256 consecutive pixels of one row.
 template <typename T, int PASS>
@@ -126,7 +115,7 @@ nlf_moments_kernel(const T* __restrict__ img, int h, int w, long pitch,
       m.mx = v > m.mx ? v : m.mx;
     }
   }
-  m = block_merge(m, lds);
+  m = block_merge<kNlfThreads>(m, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
@@ -135,9 +124,7 @@ template <int PASS>
 __global__ void __launch_bounds__(kNlfThreads)
 nlf_moments_final(const Moments* __restrict__ part, int n_part, long n_px, double* __restrict__ res) {
   __shared__ Moments lds[kNlfThreads];
-  Moments m = {0.0, __builtin_inf(), -__builtin_inf(), 0};
-  for (int p = threadIdx.x; p < n_part; p += kNlfThreads) m = merge(m, part[p]);
-  m = block_merge(m, lds);
+  const Moments m = merge_partials<kNlfThreads>(part, n_part, {0.0, __builtin_inf(), -__builtin_inf(), 0}, lds);
   if (threadIdx.x != 0) return;
   const double n = (double)(n_px - (long)m.nan);
   if (PASS) {
@@ -254,33 +241,28 @@ nlf_bins_kernel(BinArgs a) {
   }
 }
 
+struct BinTotal {
+  double sum;
+  unsigned long long n;
+};
+__device__ inline BinTotal merge(const BinTotal& a, const BinTotal& b) { return {a.sum + b.sum, a.n + b.n}; }
+
 // one workgroup per bin adds the slabs in a fixed order: thread t takes slabs t, t + 256, ..., then
 // the tree over the threads
 __global__ void __launch_bounds__(kNlfThreads)
 nlf_bins_final(const unsigned* __restrict__ slab_cnt, const double* __restrict__ slab_sum, int n_slab,
                int nbins, unsigned long long* __restrict__ cnt, double* __restrict__ sum) {
-  __shared__ double lsum[kNlfThreads];
-  __shared__ unsigned long long lcnt[kNlfThreads];
-  const int n = blockIdx.x, t = threadIdx.x;
-  unsigned long long c = 0;
-  double s = 0.0;
-  for (int g = t; g < n_slab; g += kNlfThreads) {
-    c += slab_cnt[(long)g * nbins + n];
-    s += slab_sum[(long)g * nbins + n];
+  __shared__ BinTotal lds[kNlfThreads];
+  const int n = blockIdx.x;
+  BinTotal m = {0.0, 0};
+  for (int g = threadIdx.x; g < n_slab; g += kNlfThreads) {
+    m.n += slab_cnt[(long)g * nbins + n];
+    m.sum += slab_sum[(long)g * nbins + n];
   }
-  lsum[t] = s;
-  lcnt[t] = c;
-  __syncthreads();
-  for (int k = kNlfThreads / 2; k > 0; k >>= 1) {
-    if (t < k) {
-      lsum[t] += lsum[t + k];
-      lcnt[t] += lcnt[t + k];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    cnt[n] = lcnt[0];
-    sum[n] = lsum[0];
+  m = block_merge<kNlfThreads>(m, lds);
+  if (threadIdx.x == 0) {
+    cnt[n] = m.n;
+    sum[n] = m.sum;
   }
 }
 
@@ -362,8 +344,6 @@ int persistent_grid(const ipa_ctx* ctx, long needed, int per_cu) {
   return (int)(g > 1 ? g : 1);
 }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace ipa
 
@@ -396,18 +376,15 @@ int ipa_nlf_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w
   IPA_REQUIRE(ctx, (long)h * w <= kNlfMaxPixels, "nlf_moments: more than 2^30 pixels");
   const long units = (long)h * ((w + kNlfThreads - 1) / kNlfThreads);
   const int grid = persistent_grid(ctx, units, 8);
-  const size_t part_bytes = align256((size_t)grid * sizeof(Moments));
-  int rc = ipa_ws_reserve(ctx, part_bytes + 64);
+  Moments* part;
+  double* res;
+  int rc = stage_ws(ctx, slot(&part, grid), slot(&res, 5));
   if (rc) return rc;
-  Moments* part = (Moments*)ctx->ws;
-  double* res = (double*)((char*)ctx->ws + part_bytes);
   rc = moments_pass<0>(ctx, dtype, grid, d_img, h, w, pitch, res, part);
   if (rc) return rc;
   rc = moments_pass<1>(ctx, dtype, grid, d_img, h, w, pitch, res, part);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(moments, res, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{moments, res, 5 * sizeof(double)}});
 }
 
 int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_img2, int h, int w,
@@ -429,30 +406,23 @@ int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_i
   const size_t lds = (size_t)(nbins + 1) * 8 + (size_t)waves * nbins * 12;
   const long nruns = (long)h * ((w + kRun - 1) / kRun);
   const int grid = persistent_grid(ctx, (nruns + waves * 64 - 1) / (waves * 64), 4);
-  // workspace: edges | slab sums | sums | counts | slab counts
-  const size_t o_slab_sum = align256((size_t)(nbins + 1) * 8);
-  const size_t o_sum = o_slab_sum + align256((size_t)grid * nbins * 8);
-  const size_t o_cnt = o_sum + align256((size_t)nbins * 8);
-  const size_t o_slab_cnt = o_cnt + align256((size_t)nbins * 8);
-  rc = ipa_ws_reserve(ctx, o_slab_cnt + (size_t)grid * nbins * 4);
-  if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  void *d_cnt = ws + o_cnt, *d_sum = ws + o_sum;
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  IPA_HIP(ctx, hipMemcpyAsync(ws, edges, (size_t)(nbins + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   BinArgs a;
+  double *d_edges, *d_sum;
+  unsigned long long* d_cnt;
+  const size_t slab = (size_t)grid * nbins;
+  rc = stage_ws(ctx, slot(&d_edges, nbins + 1, edges), slot(&a.slab_sum, slab), slot(&d_sum, nbins),
+                slot(&d_cnt, nbins), slot(&a.slab_cnt, slab));
+  if (rc) return rc;
   a.src = {d_img, d_img2, d_bg, pitch, pitch2, bg_pitch, bg, 1};
   a.signal = d_signal;
   a.signal_pitch = signal_pitch;
   a.h = h;
   a.w = w;
-  a.edges = (const double*)ws;
+  a.edges = d_edges;
   a.nbins = nbins;
   a.step = step;
   a.factor = factor;
   a.rms = rms;
-  a.slab_cnt = (unsigned*)(ws + o_slab_cnt);
-  a.slab_sum = (double*)(ws + o_slab_sum);
   rc = by_dtype(dtype, [&](auto e) {
     return launch(ctx, nlf_bins_kernel<decltype(e)>, dim3(grid), dim3(waves * 64), lds, a);
   });
@@ -460,10 +430,7 @@ int ipa_nlf_bins_dev(ipa_ctx* ctx, const void* d_img, int dtype, const void* d_i
   rc = launch(ctx, nlf_bins_final, dim3(nbins), dim3(kNlfThreads), 0, a.slab_cnt, a.slab_sum, grid, nbins, d_cnt,
               d_sum);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(sums, d_sum, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{counts, d_cnt, (size_t)nbins * 8}, {sums, d_sum, (size_t)nbins * 8}});
 }
 
 int ipa_snr_map_dev(ipa_ctx* ctx, const double* d_signal, int h, int w, long pitch, const double* nlf,

@@ -39,6 +39,7 @@
 #include "common.hpp"
 #include "frame_args.hpp"
 #include "launch.hpp"
+#include "reduce.hpp"
 
 #pragma clang fp contract(off)
 
@@ -177,23 +178,10 @@ poly_moments_kernel(const E* __restrict__ img, long pitch, const unsigned char* 
 }
 
 // one workgroup per entry adds the slabs: thread t takes slabs t, t + 256, .., then the tree
-__device__ inline double block_sum(double v, double* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int k = kPolyThreads / 2; k > 0; k >>= 1) {
-    if (t < k) lds[t] += lds[t + k];
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 __global__ void __launch_bounds__(kPolyThreads)
 poly_sum_columns(const double* __restrict__ part, int n_part, int ne, double* __restrict__ out) {
   __shared__ double lds[kPolyThreads];
-  double s = 0.0;
-  for (int g = threadIdx.x; g < n_part; g += kPolyThreads) s += part[(long)g * ne + blockIdx.x];
-  s = block_sum(s, lds);
+  const double s = merge_partials<kPolyThreads>(part + blockIdx.x, n_part, 0.0, lds, ne);
   if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
@@ -259,7 +247,7 @@ poly_eval_kernel(PolyCoef pc, EvalArgs a) {
     }
   }
   if (MODE != IPA_POLY_GRID && a.part) {   // uniform over the launch
-    dev = block_sum(dev, lds);
+    dev = block_merge<kPolyThreads>(dev, lds);
     if (threadIdx.x == 0) a.part[blockIdx.x] = dev;
   }
 }
@@ -322,8 +310,6 @@ clip01_kernel(E* __restrict__ img, long pitch, int h, int w, int tiles_x) {
 
 bool float_dtype(int dtype) { return dtype == IPA_F32 || dtype == IPA_F64; }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 template <typename E, int MODE>
 int eval_launch(ipa_ctx* ctx, int order, unsigned grid, const PolyCoef& pc, const EvalArgs& a) {
   const int rc = pick<0, 1, 2, 3, 4, 5>(order, [&](auto o) {
@@ -354,11 +340,9 @@ int ipa_poly2d_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, in
   cap = cap < kPolyMaxGrid ? cap : kPolyMaxGrid;
   const int grid = (int)(quads < cap ? quads : cap);
   const int iters = (int)((quads + grid - 1) / grid);
-  const size_t slab_bytes = align256((size_t)grid * ne * sizeof(double));
-  int rc = ipa_ws_reserve(ctx, slab_bytes + (size_t)ne * sizeof(double));
+  double *slab, *res;
+  int rc = stage_ws(ctx, slot(&slab, (size_t)grid * ne), slot(&res, ne));
   if (rc) return rc;
-  double* slab = (double*)ctx->ws;
-  double* res = (double*)((char*)ctx->ws + slab_bytes);
   rc = by_float(dtype, [&](auto e) {
     using E = decltype(e);
     return pick<0, 1, 2, 3, 4, 5>(order, [&](auto o) {
@@ -369,9 +353,7 @@ int ipa_poly2d_moments_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, in
   if (rc) return rc == kNotCovered ? IPA_ERR_BAD_ARG : rc;
   rc = launch(ctx, poly_sum_columns, dim3(ne), dim3(kPolyThreads), 0, slab, grid, ne, res);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(moments, res, (size_t)ne * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{moments, res, (size_t)ne * sizeof(double)}});
 }
 
 int ipa_poly2d_eval_dev(ipa_ctx* ctx, const double* coef, int order, int mode, const void* d_in, int dtype, int h,
@@ -416,11 +398,8 @@ int ipa_poly2d_eval_dev(ipa_ctx* ctx, const double* coef, int order, int mode, c
   if (rc) return rc;
   double *part = nullptr, *res = nullptr;
   if (residuum) {
-    const size_t part_bytes = align256((size_t)grid * sizeof(double));
-    rc = ipa_ws_reserve(ctx, part_bytes + sizeof(double));
+    rc = stage_ws(ctx, slot(&part, grid), slot(&res, 1));
     if (rc) return rc;
-    part = (double*)ctx->ws;
-    res = (double*)((char*)ctx->ws + part_bytes);
   }
   PolyCoef pc;
   const int nc = (order + 1) * (order + 1);
@@ -436,9 +415,7 @@ int ipa_poly2d_eval_dev(ipa_ctx* ctx, const double* coef, int order, int mode, c
   if (rc || !residuum) return rc;
   rc = launch(ctx, poly_sum_columns, dim3(1), dim3(kPolyThreads), 0, part, (int)grid, 1, res);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(residuum, res, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{residuum, res, sizeof(double)}});
 }
 
 int ipa_high_grad_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, double threshold, int size,
@@ -456,13 +433,10 @@ int ipa_high_grad_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
   IPA_REQUIRE(ctx, !overlap(span2d(d_mask, h, w, mask_pitch, 1), span2d(d_img, h, w, pitch, ipa_dtype_size(dtype))),
               "high_grad: the mask overlaps the frame");
   // workspace: the thresholded Laplacian | its dilation along x | the count
-  const size_t plane = align256((size_t)h * w);
-  rc = ipa_ws_reserve(ctx, 2 * plane + sizeof(unsigned long long));
+  unsigned char *t0, *t1;
+  unsigned long long* d_count;
+  rc = stage_ws(ctx, slot(&t0, (size_t)h * w), slot(&t1, (size_t)h * w), slot(&d_count, 1));
   if (rc) return rc;
-  unsigned char* t0 = (unsigned char*)ctx->ws;
-  unsigned char* t1 = t0 + plane;
-  unsigned long long* d_count = (unsigned long long*)(t0 + 2 * plane);
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
   IPA_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
   rc = by_float(dtype, [&](auto e) {
     return launch(ctx, laplace_mask_kernel<decltype(e)>, dim3(grid), dim3(kPolyThreads), 0, d_img, pitch, h, w, tiles_x,
@@ -477,8 +451,8 @@ int ipa_high_grad_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
               mask_pitch, d_count);
   if (rc) return rc;
   unsigned long long n = 0;
-  IPA_HIP(ctx, hipMemcpyAsync(&n, d_count, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  rc = ipa_stage_out(ctx, {{&n, d_count, sizeof(n)}});
+  if (rc) return rc;
   *count = (double)n;
   return IPA_OK;
 }

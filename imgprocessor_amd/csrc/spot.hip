@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "frame_args.hpp"
 #include "launch.hpp"
+#include "reduce.hpp"
 
 #pragma clang fp contract(off)
 
@@ -66,19 +67,6 @@ __device__ inline Range merge(const Range& a, const Range& b) {
   return {b.mn < a.mn ? b.mn : a.mn, b.mx > a.mx ? b.mx : a.mx, a.nan + b.nan, a.inf + b.inf};
 }
 
-// tree over the workgroup's threads in a fixed order; the result is thread 0's
-template <typename P>
-__device__ inline P block_merge(P v, P* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int s = kSpotThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = merge(lds[t], lds[t + s]);
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 // a unit is 256 consecutive pixels of one row
 template <typename T>
 __global__ void __launch_bounds__(kSpotThreads)
@@ -99,7 +87,7 @@ spot_range_kernel(SpotSrc s, int h, int w, Range* __restrict__ part) {
     m.mn = v < m.mn ? v : m.mn;
     m.mx = v > m.mx ? v : m.mx;
   }
-  m = block_merge(m, lds);
+  m = block_merge<kSpotThreads>(m, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
@@ -108,9 +96,7 @@ template <typename T>
 __global__ void __launch_bounds__(kSpotThreads)
 spot_range_final(SpotSrc s, const Range* __restrict__ part, int n_part, double* __restrict__ res) {
   __shared__ Range lds[kSpotThreads];
-  Range m = {__builtin_inf(), -__builtin_inf(), 0, 0};
-  for (int p = threadIdx.x; p < n_part; p += kSpotThreads) m = merge(m, part[p]);
-  m = block_merge(m, lds);
+  const Range m = merge_partials<kSpotThreads>(part, n_part, {__builtin_inf(), -__builtin_inf(), 0, 0}, lds);
   if (threadIdx.x != 0) return;
   res[0] = m.mn;
   res[1] = m.mx;
@@ -313,17 +299,6 @@ label_seam_kernel(int* __restrict__ parent, int h, int w, int tiles_x, int conn8
   }
 }
 
-__device__ inline int block_sum(int v, int* lds) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int s = kSpotThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] += lds[t + s];
-    __syncthreads();
-  }
-  return lds[0];
-}
-
 // phase 3: a block is 1024 consecutive linear indices, four per thread.  No union runs any more, so
 // a find ends at the component's final root; the pixel then points at it directly (an atomic minimum:
 // parents only ever decrease, and whoever walks through this pixel meanwhile meets an ancestor either
@@ -348,7 +323,7 @@ label_flatten_kernel(int* __restrict__ parent, long npx, int w, int* __restrict_
     labels[y * label_pitch + (i - y * w)] = r;
     c += r == (int)i;
   }
-  c = block_sum(c, lds);
+  c = block_merge<kSpotThreads>(c, lds);
   if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
@@ -479,7 +454,7 @@ largest_kernel(const unsigned long long* __restrict__ sizes, int n, Best* __rest
   Best m = {0, 0};
   for (long i = (long)blockIdx.x * kSpotThreads + threadIdx.x; i < n; i += (long)gridDim.x * kSpotThreads)
     m = merge(m, Best{(long long)sizes[i], (int)i + 1});
-  m = block_merge(m, lds);
+  m = block_merge<kSpotThreads>(m, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
@@ -487,9 +462,7 @@ largest_kernel(const unsigned long long* __restrict__ sizes, int n, Best* __rest
 __global__ void __launch_bounds__(kSpotThreads)
 largest_final(const Best* __restrict__ part, int n_part, long long* __restrict__ res) {
   __shared__ Best lds[kSpotThreads];
-  Best m = {0, 0};
-  for (int p = threadIdx.x; p < n_part; p += kSpotThreads) m = merge(m, part[p]);
-  m = block_merge(m, lds);
+  const Best m = merge_partials<kSpotThreads>(part, n_part, {0, 0}, lds);
   if (threadIdx.x != 0) return;
   res[0] = m.label;
   res[1] = m.size;
@@ -517,7 +490,7 @@ coord_sum_kernel(const int* __restrict__ labels, int h, int w, long pitch, long 
       m.x += (unsigned long long)x;
     }
   }
-  m = block_merge(m, lds);
+  m = block_merge<kSpotThreads>(m, lds);
   if (threadIdx.x == 0 && (m.y | m.x)) {
     atomicAdd((unsigned long long*)&res[2], m.y);
     atomicAdd((unsigned long long*)&res[3], m.x);
@@ -558,7 +531,7 @@ spot_take_kernel(SpotSrc s, int h, int w, const int* __restrict__ labels, long l
     if (v != v) m.nan++;
     else m.mx = v > m.mx ? v : m.mx;
   }
-  m = block_merge(m, lds);
+  m = block_merge<kSpotThreads>(m, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = m;
 }
 
@@ -566,9 +539,7 @@ spot_take_kernel(SpotSrc s, int h, int w, const int* __restrict__ labels, long l
 __global__ void __launch_bounds__(kSpotThreads)
 spot_take_final(const Take* __restrict__ part, int n_part, double* __restrict__ res) {
   __shared__ Take lds[kSpotThreads];
-  Take m = {0.0, -__builtin_inf(), 0, 0};
-  for (int p = threadIdx.x; p < n_part; p += kSpotThreads) m = merge(m, part[p]);
-  m = block_merge(m, lds);
+  const Take m = merge_partials<kSpotThreads>(part, n_part, {0.0, -__builtin_inf(), 0, 0}, lds);
   if (threadIdx.x != 0) return;
   res[0] = m.nan ? __builtin_nan("") : m.mx;
   res[1] = m.sum;
@@ -576,8 +547,6 @@ spot_take_final(const Take* __restrict__ part, int n_part, double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- host side
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // workgroups of a grid-stride launch: what the work needs, at most kSpotMaxGrid - the frame's size
 // alone decides, so that a fixed-order sum has the same order on every device
 int stride_grid(long needed) {
@@ -628,11 +597,10 @@ int ipa_spot_range_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w,
   IPA_REQUIRE(ctx, range, "spot_range: null result");
   const long units = (long)h * ((w + kSpotThreads - 1) / kSpotThreads);
   const int grid = stride_grid(units);
-  const size_t part_bytes = align256((size_t)grid * sizeof(Range));
-  rc = ipa_ws_reserve(ctx, part_bytes + 64);
+  Range* part;
+  double* res;
+  rc = stage_ws(ctx, slot(&part, grid), slot(&res, 5));
   if (rc) return rc;
-  Range* part = (Range*)ctx->ws;
-  double* res = (double*)((char*)ctx->ws + part_bytes);
   const SpotSrc src = {d_img, d_bg, pitch, bg_pitch, bg};
   rc = by_dtype(dtype, [&](auto e) {
     using T = decltype(e);
@@ -641,9 +609,7 @@ int ipa_spot_range_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w,
     return launch(ctx, spot_range_final<T>, dim3(1), dim3(kSpotThreads), 0, src, part, grid, res);
   });
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(range, res, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{range, res, 5 * sizeof(double)}});
 }
 
 int ipa_spot_histogram_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
@@ -658,15 +624,11 @@ int ipa_spot_histogram_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, in
   const size_t lds = (size_t)(nbins + 1) * 8 + (size_t)(kSpotThreads / 64) * nbins * 4;
   const long nruns = (long)h * ((w + kRun - 1) / kRun);
   const int grid = stride_grid((nruns + kSpotThreads - 1) / kSpotThreads);
-  // workspace: edges | counts | slabs
-  const size_t o_cnt = align256((size_t)(nbins + 1) * 8);
-  const size_t o_slab = o_cnt + align256((size_t)nbins * 8);
-  rc = ipa_ws_reserve(ctx, o_slab + (size_t)grid * nbins * 4);
+  double* d_edges;
+  unsigned long long* d_cnt;
+  unsigned* d_slab;
+  rc = stage_ws(ctx, slot(&d_edges, nbins + 1, edges), slot(&d_cnt, nbins), slot(&d_slab, (size_t)grid * nbins));
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  void *d_edges = ws, *d_cnt = ws + o_cnt, *d_slab = ws + o_slab;
-  IPA_HIP(ctx, hipSetDevice(ctx->device));
-  IPA_HIP(ctx, hipMemcpyAsync(d_edges, edges, (size_t)(nbins + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   const SpotSrc src = {d_img, d_bg, pitch, bg_pitch, bg};
   rc = by_dtype(dtype, [&](auto e) {
     return launch(ctx, spot_hist_kernel<decltype(e)>, dim3(grid), dim3(kSpotThreads), lds, src, h, w, d_edges, nbins,
@@ -676,9 +638,7 @@ int ipa_spot_histogram_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, in
   rc = launch(ctx, spot_hist_final, dim3((nbins + kSpotThreads - 1) / kSpotThreads), dim3(kSpotThreads), 0,
               d_slab, grid, nbins, d_cnt);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(counts, d_cnt, (size_t)nbins * 8, hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{counts, d_cnt, (size_t)nbins * 8}});
 }
 
 int ipa_spot_mask_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
@@ -714,13 +674,9 @@ int ipa_label_dev(ipa_ctx* ctx, const unsigned char* d_mask, int h, int w, long 
   const long npx = (long)h * w;
   const int tiles_x = (w + kTW - 1) / kTW, tiles = tiles_x * ((h + kTH - 1) / kTH);
   const int n_blocks = (int)((npx + kTilePx - 1) / kTilePx);
-  // workspace: parents | block counts | n
-  const size_t o_cnt = align256((size_t)npx * 4);
-  const size_t o_n = o_cnt + align256((size_t)n_blocks * 4);
-  rc = ipa_ws_reserve(ctx, o_n + 64);
+  int *parent, *counts, *d_n;
+  rc = stage_ws(ctx, slot(&parent, npx), slot(&counts, n_blocks), slot(&d_n, 1));
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  int *parent = (int*)ws, *counts = (int*)(ws + o_cnt), *d_n = (int*)(ws + o_n);
   const int conn8 = connectivity == 2;
   rc = launch(ctx, label_tile_kernel, dim3(tiles), dim3(kSpotThreads), 0, d_mask, h, w, mask_pitch, tiles_x, conn8,
               parent);
@@ -741,9 +697,7 @@ int ipa_label_dev(ipa_ctx* ctx, const unsigned char* d_mask, int h, int w, long 
   if (rc) return rc;
   rc = launch(ctx, label_write_kernel, dim3(grid), dim3(kSpotThreads), 0, parent, h, w, tx, d_labels, label_pitch);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(n, d_n, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{n, d_n, sizeof(int)}});
 }
 
 int ipa_label_sizes_dev(ipa_ctx* ctx, const int* d_labels, int h, int w, long label_pitch, int n,
@@ -769,14 +723,11 @@ int ipa_label_largest_dev(ipa_ctx* ctx, const int* d_labels, int h, int w, long 
     return IPA_OK;
   }
   const int grid = stride_grid(((long)n + kSpotThreads - 1) / kSpotThreads);
-  // workspace: sizes | partials | result
-  const size_t o_part = align256((size_t)n * 8);
-  const size_t o_res = o_part + align256((size_t)grid * sizeof(Best));
-  rc = ipa_ws_reserve(ctx, o_res + 64);
+  unsigned long long* sizes;
+  Best* d_part;
+  long long* d_res;
+  rc = stage_ws(ctx, slot(&sizes, n), slot(&d_part, grid), slot(&d_res, 4));
   if (rc) return rc;
-  char* ws = (char*)ctx->ws;
-  unsigned long long* sizes = (unsigned long long*)ws;
-  void *d_part = ws + o_part, *d_res = ws + o_res;
   rc = sizes_call(ctx, d_labels, h, w, label_pitch, n, sizes);
   if (rc) return rc;
   rc = launch(ctx, largest_kernel, dim3(grid), dim3(kSpotThreads), 0, sizes, n, d_part);
@@ -787,9 +738,7 @@ int ipa_label_largest_dev(ipa_ctx* ctx, const int* d_labels, int h, int w, long 
   rc = launch(ctx, coord_sum_kernel, dim3(stride_grid(units)), dim3(kSpotThreads), 0, d_labels, h, w, label_pitch,
               d_res);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(result, d_res, 4 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{result, d_res, 4 * sizeof(long long)}});
 }
 
 int ipa_spot_take_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch, const double* d_bg,
@@ -816,11 +765,10 @@ int ipa_spot_take_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
   const int n_rows = row_a == row_b ? 1 : 2;
   const long units = (long)(d_labels ? h : n_rows) * ((w + kSpotThreads - 1) / kSpotThreads);
   const int grid = stride_grid(units);
-  const size_t part_bytes = align256((size_t)grid * sizeof(Take));
-  rc = ipa_ws_reserve(ctx, part_bytes + 64);
+  Take* part;
+  double* res;
+  rc = stage_ws(ctx, slot(&part, grid), slot(&res, 3));
   if (rc) return rc;
-  Take* part = (Take*)ctx->ws;
-  double* res = (double*)((char*)ctx->ws + part_bytes);
   const SpotSrc src = {d_img, d_bg, pitch, bg_pitch, bg};
   rc = by_dtype(dtype, [&](auto e) {
     return launch(ctx, spot_take_kernel<decltype(e)>, dim3(grid), dim3(kSpotThreads), 0, src, h, w, d_labels,
@@ -829,9 +777,7 @@ int ipa_spot_take_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, 
   if (rc) return rc;
   rc = launch(ctx, spot_take_final, dim3(1), dim3(kSpotThreads), 0, part, grid, res);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(result, res, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{result, res, 3 * sizeof(double)}});
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "frame_args.hpp"
 #include "launch.hpp"
+#include "reduce.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -44,8 +45,6 @@ constexpr int kSepLds = 6144;             // doubles of LDS for the flat field a
 constexpr int kSepMaxCells = 1 << 16;     // grid cells, and device cells, of the separation loop
 constexpr int kSepMaxIter = 10000;
 constexpr int kTileThreads = 256;
-
-size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---- (a) partial sums of one row segment ------------------------------------------------------------------------
 template <typename E, typename B, bool HasBg>
@@ -180,6 +179,12 @@ __device__ __forceinline__ void nan_term(double v, int k, double& acc, int& cnt)
   cnt += isn ? 0 : 1;
 }
 
+// the initial flat field's maximum as reduce.hpp merges it
+struct NanMax {
+  double v;
+};
+__device__ inline NanMax merge(NanMax a, NanMax b) { return {fmax(a.v, b.v)}; }
+
 __global__ void __launch_bounds__(kSepThreads)
 steps_separate_kernel(const double* __restrict__ grid, int n, int g0, int g1, int n0, int n1,
                       const int* __restrict__ rects, double bg_value, int subtract_bg, int max_iter, double max_dev,
@@ -209,13 +214,7 @@ steps_separate_kernel(const double* __restrict__ grid, int n, int g0, int g1, in
     density[c] = cnt;
     mx = fmax(mx, m);   // np.nanmax: a NaN only where nothing else is
   }
-  s_red[t] = mx;
-  __syncthreads();
-  for (int d = kSepThreads / 2; d > 0; d >>= 1) {
-    if (t < d) s_red[t] = fmax(s_red[t], s_red[t + d]);
-    __syncthreads();
-  }
-  mx = s_red[0];
+  mx = block_merge<kSepThreads>(NanMax{mx}, (NanMax*)s_red).v;
   for (int c = t; c < G; c += kSepThreads) ff[c] = ff[c] / mx;
   __syncthreads();
 
@@ -264,6 +263,8 @@ steps_separate_kernel(const double* __restrict__ grid, int n, int g0, int g1, in
       }
       ff[c] = f2;   // only this lane reads ff[c] in this phase
     }
+    // block_merge's tree, written out on two arrays: one {sum, count} struct pads to 16 bytes, and with that 1 KiB
+    // more of LDS a compute unit holds two of these workgroups instead of three
     s_red[t] = ssq;
     s_redc[t] = sc;
     __syncthreads();
@@ -361,12 +362,10 @@ int ipa_cell_means_dev(ipa_ctx* ctx, const void* d_frames, int dtype, int n, int
                         span_stack(d_frames, n, h, w, pitch, frame_stride, ipa_dtype_size(dtype)),
                         span2d(d_bg, h, w, bg_pitch, d_bg ? ipa_dtype_size(bg_dtype) : 1)};
   IPA_REQUIRE(ctx, !written_overlaps(spans, 1), "cell_means: the grid overlaps an input");
-  // workspace: the partial sums | the partial counts
-  const size_t sum_bytes = up256((size_t)parts * sizeof(double));
-  int rc = ipa_ws_reserve(ctx, sum_bytes + (size_t)parts * sizeof(int));
+  double* part_sum;
+  int* part_cnt;
+  int rc = stage_ws(ctx, slot(&part_sum, parts), slot(&part_cnt, parts));
   if (rc) return rc;
-  double* part_sum = (double*)ctx->ws;
-  int* part_cnt = (int*)((char*)ctx->ws + sum_bytes);
   // both edge tables in one upload
   std::vector<int> edges((size_t)g0 + g1 + 2);
   memcpy(edges.data(), row_edges, ((size_t)g0 + 1) * sizeof(int));
@@ -418,23 +417,18 @@ int ipa_steps_separate_dev(ipa_ctx* ctx, const double* d_grid, int n, int g0, in
   const Span spans[] = {span2d(d_ff, 1, G, G, 8), span2d(d_avgobj, 1, D, D, 8), span2d(d_density, 1, G, G, 4),
                         span2d(d_grid, 1, (long)n * G, (long)n * G, 8)};
   IPA_REQUIRE(ctx, !written_overlaps(spans, 3), "steps_separate: an output overlaps another array");
-  // workspace: iterations | dev | the flat field and the object where LDS does not hold them
-  const bool in_lds = G + D <= kSepLds;
-  int rc = ipa_ws_reserve(ctx, 256 + (in_lds ? 0 : (size_t)(G + D) * sizeof(double)));
+  // the flat field and the object go through the workspace where LDS does not hold them (ws null: it does)
+  int* d_iter;
+  double *d_dev, *ws;
+  int rc = stage_ws(ctx, slot(&d_iter, 1), slot(&d_dev, 1), slot(&ws, G + D <= kSepLds ? 0 : G + D));
   if (rc) return rc;
-  int* d_iter = (int*)ctx->ws;
-  double* d_dev = (double*)((char*)ctx->ws + 8);
-  double* ws = in_lds ? nullptr : (double*)((char*)ctx->ws + 256);
   void* d_rects;
   rc = ipa_tab_upload(ctx, rects, (size_t)n * 6 * sizeof(int), &d_rects);
   if (rc) return rc;
   rc = launch(ctx, steps_separate_kernel, dim3(1), dim3(kSepThreads), 0, d_grid, n, g0, g1, n0, n1, d_rects, bg_value,
               subtract_bg ? 1 : 0, max_iter, max_dev, ws, d_ff, d_avgobj, d_density, d_iter, d_dev);
   if (rc) return rc;
-  IPA_HIP(ctx, hipMemcpyAsync(iterations, d_iter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipMemcpyAsync(dev, d_dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  IPA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return IPA_OK;
+  return ipa_stage_out(ctx, {{iterations, d_iter, sizeof(int)}, {dev, d_dev, sizeof(double)}});
 }
 
 int ipa_offset_meshgrid_dev(ipa_ctx* ctx, double start0, double step0, double stop0, double start1, double step1,
