@@ -47,6 +47,9 @@ EXTREMUM_MEDIAN_MAX, EXTREMUM_MIN = range(2)
 # ipa_poly_mode of ipa_poly2d_eval_dev
 POLY_FILL, POLY_ALL, POLY_GRID = range(3)
 
+# ipa_fn2d_model of ipa_fn2d_normal_dev / ipa_fn2d_eval_dev
+FN2D_KW, FN2D_AOV = range(2)
+
 # IPA_REMAP_PATH_* bits of the read-only tuning word "remap_path"
 (REMAP_PATH_GATHER, REMAP_PATH_REST, REMAP_PATH_RING, REMAP_PATH_TILE, REMAP_PATH_TILE_MAP,
  REMAP_PATH_STORED, REMAP_PATH_U8_LZ_LDS, REMAP_PATH_STRIP, REMAP_PATH_STRIP_INT, REMAP_PATH_LENS_MAP,
@@ -195,6 +198,9 @@ PROTOTYPES = {
     'ipa_steps_separate_dev': [_vp, _vp, _i, _i, _i, _i, _i, _ip, _d, _i, _i, _d, _vp, _vp, _vp, _ip, _dp],
     'ipa_offset_meshgrid_dev': [_vp, _d, _d, _d, _d, _d, _d, _i, _i, _i, _vp, _vp, _l],
     'ipa_isnan_mask_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l],
+    'ipa_fn2d_normal_dev': [_vp, _vp, _i, _i, _i, _l, _vp, _l, _i, _dp, _dp],
+    'ipa_fn2d_eval_dev': [_vp, _i, _dp, _i, _vp, _i, _i, _i, _l, _vp, _l, _vp, _vp, _i, _i, _l, _vp, _l, _dp],
+    'ipa_fn2d_divide_dev': [_vp, _vp, _i, _i, _i, _l, _d],
 }
 _CHARP = {'ipa_status_string': [_i], 'ipa_last_error': [_vp]}
 

@@ -1,1 +1,2 @@
 from .polynomial import polynomial  # noqa: F401
+from .function import function  # noqa: F401

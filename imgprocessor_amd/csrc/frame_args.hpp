@@ -1,5 +1,5 @@
-// frame_args.hpp — what the ten calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
-// ovs.hip, poly.hip, spot.hip, steps.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
+// frame_args.hpp — what the eleven calibration units (ste.hip, nlm.hip, nlf.hip, dark.hip, flat.hip, tss.hip,
+// ovs.hip, poly.hip, spot.hip, steps.hip, fn2d.hip) share.  Host side: the byte spans of pitched frames and frame stacks with their overlap checks,
 // the checks and grid of the 64 x 4 tiles, and stage_ws(): the workspace of a call as a list of typed slots over
 // ipa_stage_in (common.hpp), which ipa_stage_out answers at the call's end.  Device side, for the streaming per-pixel
 // kernels of dark / flat / tss / ovs: a lane's pixel on that tile grid and vectors of adjacent pixels.  launch.hpp holds

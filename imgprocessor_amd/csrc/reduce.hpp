@@ -1,5 +1,5 @@
 // reduce.hpp — the one workgroup reduction of the calibration units (nlf.hip, flat.hip, poly.hip, spot.hip,
-// steps.hip).  Device side.  Every fixed-order sum of those units is two stages of it:
+// steps.hip, fn2d.hip).  Device side.  Every fixed-order sum of those units is two stages of it:
 //   1  workgroup b of `grid` walks its share of the frame, every lane folds its samples into a value of its own in
 //      the order it meets them, block_merge() folds the lanes, lane 0 stores partial b;
 //   2  one workgroup: merge_partials() - lane t folds partials t, t + THREADS, ..., then block_merge() again.

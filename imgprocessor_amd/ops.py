@@ -31,6 +31,8 @@ from .ops_poly import (poly2d_moments, poly2d_gram, poly2d_solve, poly2d_eval, h
 from .ops_spot import histogram, otsu_threshold, spot_mask, label, largest_component, spot_take  # noqa: F401
 # the discrete-steps family (cell means, the separation loop, the offset grid) lives in ops_steps.py
 from .ops_steps import cell_edges, cell_means, steps_separate, offset_meshgrid, isnan_mask  # noqa: F401
+# the vignetting-function fit family (Kang-Weiss, angle of view) lives in ops_fn2d.py
+from .ops_fn2d import fn2d_normal, fn2d_eval, fn2d_divide, fn2d_fit  # noqa: F401
 
 INTERPOLATIONS = {
     # exact-coordinate forms (scipy / scikit-image semantics)

@@ -1143,6 +1143,47 @@ int ipa_offset_meshgrid_dev(ipa_ctx* ctx, double start0, double step0, double st
 int ipa_isnan_mask_dev(ipa_ctx* ctx, const void* d_in, int dtype, int h, int w, long pitch, unsigned char* d_mask,
                        long mask_pitch);
 
+/* ---- vignetting functions fitted to masked flat fields (csrc/fn2d.hip) ----------------------------
+ * camera/flatField/postprocessing/function.py with the two functions camera/flatField/postProcessing.py
+ * :50-74 fits through fancytools' fit2dArrayToFn.  The model's x is the ROW index, its y the COLUMN
+ * index.  Frames are float32 / float64 (anything else IPA_ERR_UNSUPPORTED), masks uint8 with
+ * non-zero = invalid; params is a HOST pointer.  An unknown model is IPA_ERR_BAD_ARG. */
+typedef enum {
+  IPA_FN2D_KW = 0,   /* equations/vignetting.py:21-37 with tilt = 0; params {f, alpha, cx, cy}:
+                        d = sqrt((x - cx)^2 + (y - cy)^2);  (1 / (1 + (d / f)^2)^2) * (1 - alpha d) */
+  IPA_FN2D_AOV = 1   /* equations/angleOfView.py:29-40; params {tan(a), c0, c1}, the fitted parameter is a:
+                        1 / sqrt(1 + tan(a) * (((x - c0)^2 + (y - c1)^2) / c0)) */
+} ipa_fn2d_model;
+
+/* function.py:35-37 (one evaluation of the least-squares problem curve_fit solves) - over the VALID
+ * pixels (d_mask NULL: all; a masked pixel is selected out, a NaN under the mask enters nothing),
+ * with model value m, its Jacobian J by the P fitted parameters (KW: f, alpha, cx, cy; AoV: a) and
+ * r = frame - m, sums (HOST, P (P + 1) / 2 + P + 2 doubles: 16 for KW, 4 for AoV) =
+ *   the upper triangle of J^T J by rows | J^T r | sum r^2 | the number of valid pixels.
+ * alpha * dx / d counts 0 where d == 0.  Per-workgroup partial sums are added in a fixed order by a
+ * second launch, no float atomics: two calls give identical bits.  Synchronises the stream. */
+int ipa_fn2d_normal_dev(ipa_ctx* ctx, const void* d_img, int dtype, int h, int w, long pitch,
+                        const unsigned char* d_mask, long mask_pitch, int model, const double* params, double* sums);
+
+/* function.py:35-40 - the model evaluated in double in the reference's operation order (bit for bit
+ * numpy's value) and rounded once into the frame's type; the modes are those of ipa_poly2d_eval_dev:
+ *   IPA_POLY_FILL  d_out = d_in with the pixels under d_mask replaced (d_mask NULL: all of them);
+ *                  d_out may be d_in itself (same pointer and pitch: in place)
+ *   IPA_POLY_ALL   every pixel of d_out (h x w); d_in and d_mask are ignored
+ *   IPA_POLY_GRID  d_out is gh x gw, pixel (r, c) evaluated at row position d_gy[r][c] and column
+ *                  position d_gx[r][c] (float64, grid_pitch); d_in and d_mask are ignored
+ * maximum (host, may be NULL): np.max of all of d_out, the kept pixels included - NaN if any pixel
+ * is; asking for it synchronises the stream.  An overlap of d_out with anything but an in-place d_in
+ * is IPA_ERR_BAD_ARG. */
+int ipa_fn2d_eval_dev(ipa_ctx* ctx, int model, const double* params, int mode, const void* d_in, int dtype, int h,
+                      int w, long in_pitch, const unsigned char* d_mask, long mask_pitch, const double* d_gy,
+                      const double* d_gx, int gh, int gw, long grid_pitch, void* d_out, long out_pitch,
+                      double* maximum);
+
+/* function.py:42 - img /= div in the frame's type (div rounded to it first): numpy's true division.
+ * In place. */
+int ipa_fn2d_divide_dev(ipa_ctx* ctx, void* d_img, int dtype, int h, int w, long pitch, double div);
+
 #ifdef __cplusplus
 }
 #endif
