@@ -54,6 +54,10 @@ FN2D_KW, FN2D_AOV = range(2)
 (REMAP_PATH_GATHER, REMAP_PATH_REST, REMAP_PATH_RING, REMAP_PATH_TILE, REMAP_PATH_TILE_MAP,
  REMAP_PATH_STORED, REMAP_PATH_U8_LZ_LDS, REMAP_PATH_STRIP, REMAP_PATH_STRIP_INT, REMAP_PATH_LENS_MAP,
  REMAP_PATH_FRAMES_INNER) = (1 << k for k in range(11))
+# IPA_CHAIN_PATH_* bits of the read-only tuning word "chain_path"
+(CHAIN_PATH_RESIDENT, CHAIN_PATH_STREAMED, CHAIN_PATH_SEP, CHAIN_PATH_TWO_LAUNCHES, CHAIN_PATH_RANK1,
+ CHAIN_PATH_LENS_MAP, CHAIN_PATH_ROTATED, CHAIN_PATH_STORED, CHAIN_PATH_SPLIT, CHAIN_PATH_FRAMES_WG,
+ CHAIN_PATH_PER_FRAME) = (1 << k for k in range(11))
 
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_OOM, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5
 

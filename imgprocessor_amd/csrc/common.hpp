@@ -116,6 +116,7 @@ struct ipa_ctx {
   unsigned long tile_warp_clock = 0;
   unsigned long strip_remaps = 0;     // standalone uint16 -> float32 remaps the strip kernel took (remap.hip; read like rank1_routed)
   unsigned remap_path = 0;            // IPA_REMAP_PATH_* of the kernels the last plain remap call enqueued (read the same way)
+  unsigned chain_path = 0;            // IPA_CHAIN_PATH_* of the last remap -> filter chain call (fused.hip; read the same way)
   unsigned long rank1_routed = 0;     // dense calls sent to the separable loops so far (read through ipa_ctx_get_tuning)
   int tail_rows_used = 0;             // height of the short strips of the last such launch (0: uniform strips)
   int group_chunk_used = 0;           // groups per chunk of the last launch on the shared-record loop (0: all together)

@@ -113,18 +113,25 @@ static int two_launch_remap(ipa_ctx* ctx, const ChainArgs& a, const ChainCoords&
   int rc = ipa_ws_reserve(ctx, (size_t)a.n_frames * a.dh * a.dw * 4);
   if (rc) return rc;
   const long fs = (long)a.dh * a.dw;
+  // chain_path describes the chain's own kernels: the standalone remap may run on the chains' strip launchers (remap.hip),
+  // whose bits are not this call's - what it launched stays readable as remap_path
+  const unsigned own = ctx->chain_path;
   switch (c.kind) {
     case 0:
-      return ipa_remap_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.mx, c.my, c.map_pitch, ctx->ws, IPA_F32,
-                           a.dh, a.dw, a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode, a.border_value);
+      rc = ipa_remap_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.mx, c.my, c.map_pitch, ctx->ws, IPA_F32,
+                         a.dh, a.dw, a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode, a.border_value);
+      break;
     case 1:
-      return ipa_undistort_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.K, c.dist5, c.newK, ctx->ws, IPA_F32,
-                               a.dh, a.dw, a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode,
-                               a.border_value);
+      rc = ipa_undistort_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.K, c.dist5, c.newK, ctx->ws, IPA_F32,
+                             a.dh, a.dw, a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode,
+                             a.border_value);
+      break;
     default:
-      return ipa_warp_perspective_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.M, ctx->ws, IPA_F32, a.dh, a.dw,
-                                      a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode, a.border_value);
+      rc = ipa_warp_perspective_dev(ctx, a.src, a.src_dtype, a.sh, a.sw, a.src_pitch, c.M, ctx->ws, IPA_F32, a.dh, a.dw,
+                                    a.dw, a.n_frames, a.src_frame_stride, fs, a.interp, a.border_mode, a.border_value);
   }
+  ctx->chain_path = own | IPA_CHAIN_PATH_TWO_LAUNCHES;
+  return rc;
 }
 
 // validation + everything of a FusedCall that does not depend on the filter
@@ -252,6 +259,7 @@ static int lens_through_cache(ipa_ctx* ctx, const ChainArgs& a, ChainCoords& c) 
   int rc = ipa_lens_map_cached(ctx, c.K, c.dist5, c.newK, a.dh, a.dw, &mx, &my);
   if (rc) return rc;
   c = ChainCoords{0, mx, my, a.dw};
+  ctx->chain_path |= IPA_CHAIN_PATH_LENS_MAP;
   return IPA_OK;
 }
 
@@ -264,6 +272,7 @@ static int sep_chain(ipa_ctx* ctx, const ChainArgs& a, ChainCoords c, const doub
   if (c.kind == 2) {
     rotated = a.dh > 0 && a.dw > 0 &&
               rotated_warp_in_two_launches(ctx, c.M, a.src_dtype, a.dst_dtype, a.interp, a.dh, a.dw, a.n_frames);
+    if (rotated) ctx->chain_path |= IPA_CHAIN_PATH_ROTATED;
 #if IPA_WITH_TILE_CHAIN
     if ((rc = tile_chain_try(ctx, a, c.M, ky, nky, kx, nkx, rotated)) <= 0) return rc;   // (1: not taken)
 #endif
@@ -282,12 +291,14 @@ static int dense_chain(ipa_ctx* ctx, const ChainArgs& a, ChainCoords c, const do
   if ((ctx->tune.rank1_sep & 1) && kernel && kh == kw && kh != 1 &&
       chain_one_kernel(ctx, a.src_dtype, a.dst_dtype, kind, a.interp, kh) && ipa_rank1_factor(kernel, kh, kw, ky, kx)) {
     ctx->rank1_routed++;
+    ctx->chain_path |= IPA_CHAIN_PATH_RANK1;
     return sep_chain(ctx, a, c, ky, kh, kx, kw);
   }
   int rc = lens_through_cache(ctx, a, c);
   if (rc) return rc;
   const bool rotated = c.kind == 2 && kernel && a.dh > 0 && a.dw > 0 &&
                        rotated_warp_in_two_launches(ctx, c.M, a.src_dtype, a.dst_dtype, a.interp, a.dh, a.dw, a.n_frames);
+  if (rotated) ctx->chain_path |= IPA_CHAIN_PATH_ROTATED;
   return fused_common(ctx, a, c, kernel, kh, kw, rotated);
 }
 
@@ -341,6 +352,7 @@ int ipa_remap_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int 
                             int border_mode, double border_value, int conv_border_y,
                             int conv_border_x) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, d_mapx && d_mapy && map_pitch >= dw, "bad map arguments");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};
@@ -355,6 +367,7 @@ int ipa_undistort_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, 
                                 int interp, int border_mode, double border_value, int conv_border_y,
                                 int conv_border_x) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, K && dist5 && newK, "K, dist5 and newK must be given");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};
@@ -369,6 +382,7 @@ int ipa_warp_perspective_sepconv2d_dev(ipa_ctx* ctx, const void* d_src, int src_
                                        int border_mode, double border_value, int conv_border_y,
                                        int conv_border_x) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, M, "null matrix");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};
@@ -382,6 +396,7 @@ int ipa_remap_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int sh,
                          long dst_frame_stride, int interp, int border_mode, double border_value,
                          int conv_border_x, int conv_border_y) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, d_mapx && d_mapy && map_pitch >= dw, "bad map arguments");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};
@@ -396,6 +411,7 @@ int ipa_undistort_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dtype, int
                              int border_mode, double border_value, int conv_border_x,
                              int conv_border_y) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, K && dist5 && newK, "K, dist5 and newK must be given");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};
@@ -409,6 +425,7 @@ int ipa_warp_perspective_conv2d_dev(ipa_ctx* ctx, const void* d_src, int src_dty
                                     long dst_frame_stride, int interp, int border_mode,
                                     double border_value, int conv_border_x, int conv_border_y) {
   if (!ctx) return IPA_ERR_BAD_ARG;
+  ctx->chain_path = 0;
   IPA_REQUIRE(ctx, M, "null matrix");
   const ChainArgs a{d_src, src_dtype, sh, sw, src_pitch, d_dst, dst_dtype, dh, dw, dst_pitch, n_frames, src_frame_stride,
                     dst_frame_stride, interp, border_mode, border_value, conv_border_x, conv_border_y};

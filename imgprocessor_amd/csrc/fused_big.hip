@@ -26,6 +26,7 @@ static void fused_big_launch_one(ipa_ctx* ctx, const FusedCall& f) {
   dim3 grid = wave_grid(ctx, a.p, f.n_frames, IPA_WPB, true, coord_is_table<typename Src::coord_type>::value, false, K),
        block(64 * IPA_WPB);
   hipLaunchKernelGGL((wave_stencil_big_kernel<Src, K>), grid, block, 0, ctx->stream, a);
+  chain_launched(ctx, IPA_CHAIN_PATH_STREAMED, a.p);
 }
 
 }  // namespace ipa

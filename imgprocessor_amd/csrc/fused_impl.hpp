@@ -103,11 +103,14 @@ static int fused_batch(ipa_ctx* ctx, const FusedCall& f, const Coord& c, const L
   if constexpr (std::is_same<Coord, HomographyCoord>::value && capable) {
     if (ctx->tune.stored_coords > 0 && f.n_frames >= ctx->tune.stored_coords && plan != kPerFrameLoop) {
       StoredCoord<double> sc;
-      if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0)
+      if (stored_coords_prepare<Coord>(ctx, c, f.p.dh, f.p.dw, &sc) == 0) {
+        ctx->chain_path |= IPA_CHAIN_PATH_STORED;
         return fused_batch<ST, INTERP, K, Capable>(ctx, f, sc, launch);
+      }
     }
   }
   if (plan == kSharedSplit) {
+    ctx->chain_path |= IPA_CHAIN_PATH_SPLIT;
     const int rc = fused_batch<ST, INTERP, K, Capable>(ctx, part[0], c, launch);
     return rc ? rc : fused_batch<ST, INTERP, K, Capable>(ctx, part[1], c, launch);
   }
@@ -135,6 +138,7 @@ static void fused_launch_one(ipa_ctx* ctx, const FusedCall& call, const Coord& c
                           coord_is_table<typename Src::coord_type>::value || shared_capable<Src, K>::value, false, K);
     dim3 block(64 * IPA_WPB);
     hipLaunchKernelGGL((wave_stencil_kernel<Src, K>), grid, block, 0, ctx->stream, p, s, w);
+    chain_launched(ctx, IPA_CHAIN_PATH_RESIDENT, p);
     return IPA_OK;
   });
 }

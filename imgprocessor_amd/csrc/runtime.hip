@@ -140,6 +140,10 @@ int ipa_ctx_get_tuning(ipa_ctx* ctx, const char* name, int* value) {
     *value = (int)ctx->remap_path;
     return IPA_OK;
   }
+  if (strcmp(name, "chain_path") == 0) {
+    *value = (int)ctx->chain_path;
+    return IPA_OK;
+  }
   if (strcmp(name, "tail_rows_used") == 0) {
     *value = ctx->tail_rows_used;
     return IPA_OK;

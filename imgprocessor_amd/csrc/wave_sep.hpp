@@ -423,6 +423,7 @@ static int launch_sep(ipa_ctx* ctx, WaveParams p, const Src& src, const double* 
   }
   const dim3 grid = sep_grid<Src, K>(ctx, p, n_frames);   // (fills p: before the launch takes it)
   hipLaunchKernelGGL((wave_sep_kernel<Src, K, DT>), grid, dim3(256), 0, ctx->stream, p, src, w, xcval);
+  if constexpr (!std::is_same<Src, LoadRowSrc>::value) chain_launched(ctx, IPA_CHAIN_PATH_SEP, p);   // a sampling source
   IPA_HIP(ctx, hipGetLastError());
   return IPA_OK;
 }

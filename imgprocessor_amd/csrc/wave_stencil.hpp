@@ -268,6 +268,12 @@ static inline dim3 wave_grid(ipa_ctx* ctx, WaveParams& p, int n_frames, int wave
   return dim3(blocks, (unsigned)n_frames);
 }
 
+// the launch record of the remap -> filter chains (ipa_ctx::chain_path): the kernel a chain launcher enqueued and the
+// frames_wg that wave_grid / sep_grid left in the launch's WaveParams
+static inline void chain_launched(ipa_ctx* ctx, unsigned kernel_bit, const WaveParams& p) {
+  ctx->chain_path |= kernel_bit | (p.frames_wg ? IPA_CHAIN_PATH_FRAMES_WG : IPA_CHAIN_PATH_PER_FRAME);
+}
+
 // How a batch runs on a kernel with the shared-record loop (wave_run_strip_shared: the waves of a workgroup are IPA_WPB
 // frames of one strip that share their footprint records through LDS).  `capable`: the kernel's own trait
 // (shared_capable / sep_shared, plus IPA_PIPE_EDGE where the rim strips must take the loop too).

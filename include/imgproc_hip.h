@@ -100,6 +100,10 @@ int ipa_ctx_synchronize(ipa_ctx* ctx);
  *   entry - ipa_undistort_dev's pass through its cached map into ipa_remap_dev keeps one word for the whole call; after
  *   a remap -> filter chain of two launches it describes that chain's remap -, every launch site sets its bit where the
  *   kernel is enqueued.  Written on the host, once per launch; no routing decision reads it.
+ *   Read-only "chain_path": what the last remap -> filter chain call (the six ipa_*_conv2d_dev / ipa_*_sepconv2d_dev
+ *   exports with a coordinate source) did, as IPA_CHAIN_PATH_* bits (below).  The export clears the word on entry; every
+ *   bit is set where the thing happens, from what the launch used.  The word describes the chain's own kernels: what the
+ *   remap of a chain of two launches enqueued stays in "remap_path".  Written on the host; no routing decision reads it.
  *   "sep_u16" (uint16 frames, bilinear remap by maps or a homography -> separable 3 / 5 / 7 / 9-tap filter in one kernel: default 1;
  *   0 = two launches through the workspace).
  *   "tail_rows" (chunked batches on the shared-record loop end every XCD's share of the launch on short strips -
@@ -127,6 +131,19 @@ enum {                                    /* bits of the read-only "remap_path" 
   IPA_REMAP_PATH_STRIP_INT = 1 << 8,    /* ... into the frames' own integer type */
   IPA_REMAP_PATH_LENS_MAP = 1 << 9,     /* ipa_undistort_dev through its cached map */
   IPA_REMAP_PATH_FRAMES_INNER = 1 << 10 /* the gather / rest launch had the frame index fastest */
+};
+enum {                                    /* bits of the read-only "chain_path" (csrc/fused.hip, fused_impl.hpp, fused_big.hip, wave_sep.hpp) */
+  IPA_CHAIN_PATH_RESIDENT = 1 << 0,     /* wave_stencil_kernel with a sampling source: dense 3 / 5 / 7 taps */
+  IPA_CHAIN_PATH_STREAMED = 1 << 1,     /* wave_stencil_big_kernel with a sampling source: dense 7 / 9 / 11 taps */
+  IPA_CHAIN_PATH_SEP = 1 << 2,          /* wave_sep_kernel with a sampling source */
+  IPA_CHAIN_PATH_TWO_LAUNCHES = 1 << 3, /* the remap into the workspace, then the plain filter */
+  IPA_CHAIN_PATH_RANK1 = 1 << 4,        /* a dense kernel that is an outer product went to the separable chain */
+  IPA_CHAIN_PATH_LENS_MAP = 1 << 5,     /* the lens model was replaced by its cached map */
+  IPA_CHAIN_PATH_ROTATED = 1 << 6,      /* a rotated homography: two launches preferred to the one kernel */
+  IPA_CHAIN_PATH_STORED = 1 << 7,       /* a homography's coordinates read from the table evaluated once */
+  IPA_CHAIN_PATH_SPLIT = 1 << 8,        /* the batch ran as head and tail launches of the shared-record loop */
+  IPA_CHAIN_PATH_FRAMES_WG = 1 << 9,    /* a launch whose workgroups were frames of one strip (WaveParams::frames_wg = 1) */
+  IPA_CHAIN_PATH_PER_FRAME = 1 << 10    /* a launch whose waves each had a strip of their own (frames_wg = 0) */
 };
 int ipa_ctx_set_tuning(ipa_ctx* ctx, const char* name, int value);
 int ipa_ctx_get_tuning(ipa_ctx* ctx, const char* name, int* value);

@@ -7,7 +7,8 @@ of the suite.  Here the exports are called directly (ctx._lib) with wrap along o
 the other, both ways round, on every route a chain can take: the resident strip kernel (dense 3 x 3), the
 rank-1 route (outer(g5, g5) -> the separable loop), the separable loop (7 + 7), the streamed kernel (dense
 9 x 9; with maps - the other coordinate sources run it as two launches) and the two launches (bicubic +
-separable 5 + 5).  n = 1 is the per-frame loop, n = 4 the shared-record loop.
+separable 5 + 5).  n = 1 is the per-frame loop, n = 4 the shared-record loop.  Every call's launch record
+(ctx.get_tuning('chain_path')) is held against route() below, which states all of this case by case.
 
 Expected: the oracle's remap of each frame (float32), then tests/conv_ref.py's ref_conv2d / ref_sepconv2d
 with mode (columns) and mode_y (rows) set per axis, within that file's bound().  Every case first shows, on
@@ -86,6 +87,22 @@ def scene(ia, oracle):
             'mid': mid}
 
 
+def route(coords, fname, n):
+    """the launch record of a case, from fused.hip's rules: the kernel by filter and coordinate source; LENS_MAP
+    where the lens model goes through its cached map; FRAMES_WG for the four frames of a one-kernel chain,
+    PER_FRAME for one; STORED for four frames under a homography on the shared-record loop"""
+    from imgprocessor_amd import _lib as L
+    kernel = {'dense3': L.CHAIN_PATH_RESIDENT, 'rank1_5': L.CHAIN_PATH_RANK1 | L.CHAIN_PATH_SEP,
+              'sep7': L.CHAIN_PATH_SEP, 'cubic_sep5': L.CHAIN_PATH_TWO_LAUNCHES,
+              'dense9': L.CHAIN_PATH_STREAMED if coords in ('maps', 'lens') else L.CHAIN_PATH_TWO_LAUNCHES}[fname]
+    path = kernel | (L.CHAIN_PATH_LENS_MAP if coords == 'lens' else 0)
+    if kernel & L.CHAIN_PATH_TWO_LAUNCHES:
+        return path
+    if coords == 'homography' and n == 4:
+        path |= L.CHAIN_PATH_STORED
+    return path | (L.CHAIN_PATH_FRAMES_WG if n == 4 else L.CHAIN_PATH_PER_FRAME)
+
+
 def expected(mids, filt, bx, by, n):
     """the reference and its bound for the first n frames; asserts that swapped modes could not pass"""
     ref = ref_sepconv2d if isinstance(filt, tuple) else ref_conv2d
@@ -147,10 +164,12 @@ def test_filter_border_per_axis(ia, scene, coords, fname, bx, by, n):
         before = ctx.get_tuning('rank1_routed')
         got = call_chain(ia, scene, coords, filt, interp, n, bx, by)
         routed = ctx.get_tuning('rank1_routed') - before
+        path = ctx.get_tuning('chain_path')
     finally:
         if old:
             ctx.set_tuning(**old)
     assert routed == (1 if fname == 'rank1_5' else 0), 'rank-1 route'
+    assert path == route(coords, fname, n), 'chain_path %#x, expected %#x' % (path, route(coords, fname, n))
     for f in range(n):
         err = np.abs(got[f].astype(np.float64) - want[f])
         worst = np.unravel_index(np.argmax(err - tol[f]), err.shape)

@@ -27,6 +27,13 @@ def gauss(k, sigma=1.0):
     return g / g.sum()
 
 
+def taps(k, seed):
+    """k positive taps with no symmetry, normalised (a reversed tap order, or ky and kx exchanged, gives another
+    picture: the Gaussians above would hide either)"""
+    t = np.random.default_rng(seed).random(k) + 0.1
+    return t / t.sum()
+
+
 def routed(ctx):
     return ctx.get_tuning('rank1_routed')
 
@@ -38,7 +45,8 @@ def test_rank1_chain_is_the_separable_chain(ia, oracle, K):
     h, w, n = 140, 610, 4
     src = frames(n, h, w)
     mx, my, _, _ = radial_maps(h, w)
-    ky, kx = gauss(K), gauss(K, 0.8)            # an asymmetric outer product
+    ky, kx = taps(K, 40 + K), taps(K, 50 + K)   # an outer product of two different factors, neither symmetric
+    assert not np.allclose(ky, ky[::-1], rtol=0.05) and not np.allclose(kx, kx[::-1], rtol=0.05)
     k = np.outer(ky, kx)
     d_src, dmx, dmy = ctx.to_device(src), ctx.to_device(mx), ctx.to_device(my)
     before = routed(ctx)
@@ -173,13 +181,13 @@ def test_plain_filter_rank1(ia, oracle):
     img = frames(3, 150, 600)
     d = ctx.to_device(img)
     for K, expect in ((3, 0), (5, 0), (7, 0), (9, 1)):
-        k = np.outer(gauss(K), gauss(K, 1.3))
+        k = np.outer(taps(K, 60 + K), taps(K, 70 + K))
         before = routed(ctx)
         got = ops.conv2d(d, k).get()
         assert routed(ctx) == before + expect, K
         want = oracle.conv2d(img[1], k)
         assert_close(got[1], want, 1e-5, 1e-5 * np.abs(want).max(), 'plain K=%d' % K)
-    k9 = np.outer(gauss(9), gauss(9))
+    k9 = np.outer(taps(9, 81), taps(9, 82))
     before = routed(ctx)
     got = ops.conv2d(d, k9, mode='constant', cval=0.3).get()       # does not factor: dense
     assert routed(ctx) == before

@@ -118,6 +118,14 @@ LOOPS = {
 }
 
 
+def loop_bit(loop, n):
+    """what chain_path must say of a one-kernel chain of n frames under LOOPS[loop]: whole workgroups of frames
+    (the shared-footprint loop where the kernel has one) under the first two, a strip per wave under the others"""
+    from imgprocessor_amd import _lib as L
+    shared = loop in ('default policy', 'shared-footprint loop') and n % 4 == 0
+    return L.CHAIN_PATH_FRAMES_WG if shared else L.CHAIN_PATH_PER_FRAME
+
+
 @pytest.mark.parametrize('loop', list(LOOPS))
 @pytest.mark.parametrize('K', [3, 5, 7])
 def test_every_lane_of_the_rim_strip(ia, oracle, loop, K):
@@ -126,8 +134,11 @@ def test_every_lane_of_the_rim_strip(ia, oracle, loop, K):
     reflected halo lanes: which lanes lost pixel (0, 0) depended on their neighbours' offsets (column 7: wrong,
     column 1: right).  Round 5's rule (make VARIANT=r5corner DEFS=-DIPA_DEBUG_CORNER_AS_ROUND5 ONLY="fused_k3 fused_k5 ...")
     fails the default policy and the shared-footprint loop at 3x3 and 5x5, first with the corner in column 3."""
-    from imgprocessor_amd import ops
+    from imgprocessor_amd import ops, _lib as L
     ctx = ia.default_context(0)
+    # 3 x 3 and 5 x 5: the resident kernel, whose four frames share footprint records; float32 frames + 7 x 7 from
+    # maps: the streamed kernel (no such loop: frames_wg is an order there) - under a homography the resident one
+    kernel = L.CHAIN_PATH_RESIDENT if K <= 5 else L.CHAIN_PATH_STREAMED
     h, w, dh = 143, 1052, 120
     src = frames(4, h, w)
     src[:, 0, 0] = 2.0
@@ -140,12 +151,15 @@ def test_every_lane_of_the_rim_strip(ia, oracle, loop, K):
             for n in (4, 1):
                 mx, my = (x - (c + 0.3)).astype(np.float32), (y - 5.4).astype(np.float32)
                 got = ops.remap_conv2d(d[n], ctx.to_device(mx), ctx.to_device(my), k, 'linear', 'constant', 0.25).get()
+                assert ctx.get_tuning('chain_path') == kernel | loop_bit(loop, n), (loop, K, n)
                 for f in (0, n - 1):
                     want = oracle.conv2d(oracle.remap(src[f], mx, my, oracle.LINEAR, oracle.CONSTANT, 0.25), k)
                     assert_close(got[f], want, 1e-5, 2e-5, '%s, %dx%d, corner in column %d, frame %d of %d' % (loop, K, K, c, f, n))
         # the fuzzer's own matrix (a rotation of 2 degrees on top), as a homography
         M = np.array([[1.005, -0.037, -1.459], [0.04, 1.006, -50.734], [0.0, 0.0, 0.997]])
         got = ops.warp_perspective_conv2d(d[4], M, (dh, w), k, 'linear', 'constant', 0.25).get()
+        stored = L.CHAIN_PATH_STORED if loop == 'default policy' else 0     # (the other sets have stored_coords = 0)
+        assert ctx.get_tuning('chain_path') == L.CHAIN_PATH_RESIDENT | stored | loop_bit(loop, 4), (loop, K)
         for f in (0, 3):
             want = oracle.conv2d(oracle.warp_perspective(src[f], M, (dh, w), oracle.LINEAR, oracle.CONSTANT, 0.25), k)
             assert_close(got[f], want, 1e-5, 2e-5, '%s, %dx%d, homography, frame %d' % (loop, K, K, f))
@@ -160,7 +174,7 @@ def test_last_pixel_of_uint16_frames(ia, oracle, loop):
     the pixel with it (tools/fuzz_corners.py, round 6: 405 of 4095 off in 2 samples per frame, every frame of the
     batch - at 12 x 170 px and 116 x 65 px frames, not at 23 x 170: it depends on where the frame ends, so the
     frame size is swept through every residue of 16 bytes and both failing geometries are here as drawn)."""
-    from imgprocessor_amd import ops
+    from imgprocessor_amd import ops, _lib as L
     ctx = ia.default_context(0)
     k = kern(3)
     cases = [(12, 170, 71, 340, 12, np.array([[9.99999272e-01, 1.20700418e-03, -4.71179433], [-1.20700418e-03, 9.99999272e-01, -38.236679],
@@ -181,10 +195,53 @@ def test_last_pixel_of_uint16_frames(ia, oracle, loop):
             d = ctx.to_device(src)
             plain = ops.remap(d, dmx, dmy, 'linear', 'constant', 17).get()
             got = ops.remap_conv2d(d, dmx, dmy, k, 'linear', 'constant', 17.0).get()
+            assert ctx.get_tuning('chain_path') == L.CHAIN_PATH_RESIDENT | loop_bit(loop, n), (loop, h, w, n)
             for f in (0, n - 1):
                 assert np.array_equal(plain[f], oracle.remap(src[f], mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0)), (h, w, n, f)
                 mid = oracle.remap(src[f], mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0, out_dtype=np.float32)
                 assert_close(got[f], oracle.conv2d(mid, k), 1e-5, 0.04, '%s, %d frames of %d x %d px, frame %d' % (loop, n, h, w, f))
+    finally:
+        ctx.set_tuning(**old)
+
+
+@pytest.mark.parametrize('loop', list(LOOPS))
+def test_last_pixel_of_uint8_frames(ia, oracle, loop):
+    """the same corner of uint8 frames: a tap row is two BYTES, so the 16-bit load whose left tap is the last pixel
+    of the last row ends one byte past the frame - the geometries of the uint16 test as drawn and the frame width
+    swept through every residue of 16 bytes (23 rows: 23 w runs through all of them), the same loops, the same
+    comparison: the plain remap equal to the oracle's uint8 result, the chain within rtol 1e-5 + 1e-5 x 255."""
+    from imgprocessor_amd import ops, _lib as L
+    ctx = ia.default_context(0)
+    k = kern(3)
+    cases = [(12, 170, 71, 340, 12, np.array([[9.99999272e-01, 1.20700418e-03, -4.71179433], [-1.20700418e-03, 9.99999272e-01, -38.236679],
+                                                [0.0, 0.0, 1.0]])),
+             (116, 65, 160, 108, 8, np.array([[1.04, 0.0, -7.25123345], [0.0, 1.04, -15.95355581], [0.0, 0.0, 1.0]]))]
+    for h in (12, 23):
+        for w in range(160, 177):
+            cases.append((h, w, h + 20, w + 40, 4, np.array([[1.0, 0.0, -7.3], [0.0, 1.0, -5.4], [0.0, 0.0, 1.0]])))
+    assert {(23 * w) % 16 for w in range(160, 177)} == set(range(16))
+    old = ctx.set_tuning(**LOOPS[loop])
+    try:
+        for h, w, dh, dw, n, M in cases:
+            y, x = np.mgrid[0:dh, 0:dw].astype(np.float64)
+            mx = (M[0, 0] * x + M[0, 1] * y + M[0, 2]).astype(np.float32)
+            my = (M[1, 0] * x + M[1, 1] * y + M[1, 2]).astype(np.float32)
+            dmx, dmy = ctx.to_device(mx), ctx.to_device(my)
+            src = np.round(frames(n, h, w).astype(np.float64) * 255).astype(np.uint8)
+            src[:, -1, -1] = 255
+            # the last pixel is sampled, and matters: a zero in its place gives another remapped frame
+            z = src[0].copy()
+            z[-1, -1] = 0
+            assert not np.array_equal(oracle.remap(z, mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0, out_dtype=np.float32),
+                                      oracle.remap(src[0], mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0, out_dtype=np.float32))
+            d = ctx.to_device(src)
+            plain = ops.remap(d, dmx, dmy, 'linear', 'constant', 17).get()
+            got = ops.remap_conv2d(d, dmx, dmy, k, 'linear', 'constant', 17.0).get()
+            assert ctx.get_tuning('chain_path') == L.CHAIN_PATH_RESIDENT | loop_bit(loop, n), (loop, h, w, n)
+            for f in (0, n - 1):
+                assert np.array_equal(plain[f], oracle.remap(src[f], mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0)), (h, w, n, f)
+                mid = oracle.remap(src[f], mx, my, oracle.LINEAR, oracle.CONSTANT, 17.0, out_dtype=np.float32)
+                assert_close(got[f], oracle.conv2d(mid, k), 1e-5, 1e-5 * 255, '%s, %d frames of %d x %d px, frame %d' % (loop, n, h, w, f))
     finally:
         ctx.set_tuning(**old)
 

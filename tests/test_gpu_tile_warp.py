@@ -175,24 +175,35 @@ def test_repeated_calls_with_changing_homographies(ia):
 def test_rotated_fused_chains_in_two_launches_have_the_same_bits(ia):
     """warp + filter of a batch the tile kernel takes, under a rotation: tile warp into the
     workspace, then the filter (fused.hip: rotated_warp_in_two_launches) - the bits of the one
-    fused kernel"""
+    fused kernel.  The rule answers yes from a row drift of 0.2 px per px on (sin of 11.6 degrees): 15 degrees
+    here - at the 5 degrees this test had until the chains got their launch record, tile_warp = 1 ran the one
+    kernel too and the test compared it with itself.  chain_path is the evidence: ROTATED | TWO_LAUNCHES at
+    tile_warp = 1, neither at 0 (the separable kernel on stored coordinates, whole workgroups of frames)."""
     from imgprocessor_amd import ops
     ctx = ia.default_context(0)
     n, h, w = 8, 2160, 3840
     rng = np.random.default_rng(3)
     d = ctx.to_device(rng.random((n, h, w), dtype=np.float32))
-    M = rot_persp(h, w, 5.0, persp=(2e-6, 1e-6))
+    M = rot_persp(h, w, 15.0, persp=(2e-6, 1e-6))
     g9 = ops.gaussian_kernel1d(1.0)
     k5 = np.outer(g9[2:7], g9[2:7])
     k5 /= k5.sum()
-    out = {}
+    out, path = {}, {}
     try:
         for tw in (0, 1):
             ctx.set_tuning(tile_warp=tw)
-            out[tw] = (ops.warp_perspective_sepconv2d(d, M, (h, w), g9, g9).get(),
-                       ops.warp_perspective_conv2d(d, M, (h, w), k5).get())
+            sep = ops.warp_perspective_sepconv2d(d, M, (h, w), g9, g9).get()
+            path[tw, 'sep'] = ctx.get_tuning('chain_path')
+            dense = ops.warp_perspective_conv2d(d, M, (h, w), k5).get()
+            path[tw, 'dense'] = ctx.get_tuning('chain_path')
+            out[tw] = (sep, dense)
     finally:
         ctx.set_tuning(tile_warp=1)
+    one = _lib.CHAIN_PATH_SEP | _lib.CHAIN_PATH_STORED | _lib.CHAIN_PATH_FRAMES_WG
+    two = _lib.CHAIN_PATH_ROTATED | _lib.CHAIN_PATH_TWO_LAUNCHES
+    assert path[1, 'sep'] == two and path[0, 'sep'] == one, path
+    # (the 5 x 5 is an outer product: the rank-1 route hands it to the separable chain first)
+    assert path[1, 'dense'] == two | _lib.CHAIN_PATH_RANK1 and path[0, 'dense'] == one | _lib.CHAIN_PATH_RANK1, path
     same_bits(out[1][0], out[0][0], 'warp + separable 9+9')
     same_bits(out[1][1], out[0][1], 'warp + dense 5x5')
 
