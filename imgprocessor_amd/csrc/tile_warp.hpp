@@ -33,26 +33,6 @@ namespace ipa {
 // 32 x 32 and 32 x 16 for homographies that shrink parts of the picture (PerspectiveCorrection's
 // uncorrect / distort, strong trapezoids: a 64 x 32 tile of the far side can span 180 x 96 source
 // pixels).  TW = 64: lane = column, wave + 4 j = row; TW = 32: lanes 0-31 / 32-63 = two rows.
-#ifndef IPA_TILE_SLOW_INSIDE
-#define IPA_TILE_SLOW_INSIDE 1    // 0 (round 6, measured with IPA_TILE_RECOMPUTE = 1: slower, off): the rare tap-by-tap footprints of
-                                  // float32 frames in a frame loop of their own behind the main one
-#endif
-#ifndef IPA_TILE_CUBIC_READS_FIRST
-#define IPA_TILE_CUBIC_READS_FIRST 1   // 0: the taps of a pixel pair read and summed row by row
-#endif
-#ifndef IPA_TILE_PITCH_ODD
-#define IPA_TILE_PITCH_ODD 0      // 1: the LDS box pitch among the odd candidates only (rounds 4 - 5)
-#endif
-#ifndef IPA_LZ_TABLE_STRIDE12
-#define IPA_LZ_TABLE_STRIDE12 1   // 0: the Lanczos4 weight table with rows of 8 floats (rounds 4 - 5)
-#endif
-#ifndef IPA_TILE_RECOMPUTE
-#define IPA_TILE_RECOMPUTE 0      // 1 (round 6, measured slower, off): the frame loop's scalar invariants recomputed per frame on
-                                  // the scalar unit instead of hoisted and restored with v_readlane_b32 - see the frame loop
-#endif
-#ifndef IPA_TILE_CUBIC_PACKED
-#define IPA_TILE_CUBIC_PACKED 1   // 0: the scalar bicubic loop of rounds 4 - 5 (same bits; tuning A/B builds)
-#endif
 constexpr int kWarpShapes = 3;
 constexpr int kWarpTileWs[kWarpShapes] = {64, 32, 32}, kWarpTileHs[kWarpShapes] = {32, 32, 16};
 constexpr int kWarpTileLdsBytes = 40960;  // the box of one tile (4 workgroups per CU at the most)
@@ -188,7 +168,7 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
   // start on the same bank and the 16 lanes of a ds_read_b128 group pile up 2 - 4 deep on them (a fifth of the
   // kernel's LDS cycles were bank conflicts, and its LDS arrays are busy 77 % of the launch); at 12 only r and r + 16 meet.
   // (uint16 frames, Lanczos4: the same table, the same reads; uint16 bicubic keeps its 4-float rows behind 256 floats)
-  constexpr int kLzStride = (kLz && IPA_LZ_TABLE_STRIDE12) ? 12 : 8;
+  constexpr int kLzStride = kLz ? 12 : 8;
   __shared__ __attribute__((aligned(16))) float lz[kLz ? 32 * kLzStride : (kU16 ? 384 : 4)];
   const unsigned tid = threadIdx.x, lane = tid & 63u;
   const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -531,18 +511,10 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
   // when the frame's turn has come: without the 16 prefetch registers 0.862 -> 0.838 ms per 16 x 4K)
   constexpr bool kPrefetch = !(kU16 && kLz);
   if (kPrefetch && direct && f0 < f1) box_issue(RimT{}, s.rsrc);
+  // (the loop's scalar invariants stay hoisted, ~70 of them restored per frame with v_readlane_b32: recomputed per
+  // frame on the scalar unit they measured slower, round 6 - 16 x 4K bicubic 0.303 -> 0.324 ms, bilinear 0.304 -> 0.381)
 #pragma unroll 1
   for (unsigned f = f0; f < f1; f++) {
-#if IPA_TILE_RECOMPUTE
-    // Round 6: everything the frame loop derives from the box's first row, its height and the tile's first row -
-    // the 10 + 4 row offsets of the box loads, the per-row store predicates of the fill, the 8 row offsets of the
-    // result stores - is loop-invariant, so the compiler forms it once, runs out of scalar registers (102) and
-    // restores ~70 of those values per frame with v_readlane_b32: VECTOR instructions in a kernel whose SIMDs issue
-    // 70 - 88 % of the launch.  Opaque copies make it recompute them on the scalar unit instead - MEASURED SLOWER
-    // (16 x 4K: bicubic 0.303 -> 0.324 ms, under 15 degrees 0.409 -> 0.468, bilinear 0.304 -> 0.381; Lanczos4 level):
-    // the recomputed multiplies and selects sit in front of the loads that need them, the restores did not.  Off.
-    asm volatile("" : "+s"(by0), "+s"(bh), "+s"(y0));
-#endif
     s.rsrc = make_rsrc(a.src + (long)f * a.src_frame_bytes, a.src_bytes);
     __syncthreads();   // the previous frame's taps are read (first pass: the Lanczos table is written)
     // 1. the box
@@ -635,9 +607,6 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
         // (counted s_waitcnt lgkmcnt(8): the 8 reads of the older pair have returned - LDS reads
         // return in order, anything else in flight only makes the wait stricter).
         auto issue = [&](v2f (&t)[8]) {
-#ifdef IPA_DEBUG_LZ_HALF_READS   // measurement only (WRONG results): every other sample re-uses the taps in the registers
-          if (j & 1) return;
-#endif
           static_for<0, 8>([&](auto cc) {
             constexpr int c = decltype(cc)::value;
             t[c] = lds_read_b64<c * 8>(ra);
@@ -700,7 +669,7 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
           store_px(o, y);
         __builtin_amdgcn_sched_barrier(0);   // one sample's taps in flight
       }
-    } else if constexpr (INTERP == kCubic && !kU16 && IPA_TILE_CUBIC_PACKED != 0 && kWarpTilePx % 2 == 0) {
+    } else if constexpr (INTERP == kCubic && !kU16 && kWarpTilePx % 2 == 0) {
       // bicubic on float32 frames, two pixels of the thread at a time in the halves of packed instructions (round
       // 6): the Keys weights of both (cubic_weights<v2f>), then per tap row one packed multiply and three packed
       // fmas on (tap of pixel a, tap of pixel b) - 20 vector instructions for the 2 x 16 taps instead of 40, 14
@@ -721,7 +690,6 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
         // and their latency stood in front of every tap row - the kernel neither issued (0.70) nor kept its LDS
         // arrays busy (0.47))
         typedef const volatile __attribute__((address_space(3))) float* lds_vf;
-#if IPA_TILE_CUBIC_READS_FIRST
         v2f tp[4][4];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -737,17 +705,6 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
           for (int c = 1; c < 4; c++) rs = ipa_fma(wx[c], tp[r][c], rs);
           o = r == 0 ? wy[0] * rs : ipa_fma(wy[r], rs, o);
         }
-#else
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          lds_vf tra = (lds_vf)(tpa + r * a.pitch);
-          lds_vf trb = (lds_vf)(tpb + r * a.pitch);
-          v2f rs = wx[0] * v2f{tra[0], trb[0]};
-#pragma unroll
-          for (int c = 1; c < 4; c++) rs = ipa_fma(wx[c], v2f{tra[c], trb[c]}, rs);
-          o = r == 0 ? wy[0] * rs : ipa_fma(wy[r], rs, o);
-        }
-#endif
         if (ad[j0] >= 0 && x < a.dw && ya < a.dh) store_px(o.x, ya);
         if (ad[j0 + 1] >= 0 && x < a.dw && yb < a.dh) store_px(o.y, yb);
         __builtin_amdgcn_sched_barrier(0);
@@ -796,11 +753,9 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
       __builtin_amdgcn_sched_barrier(0);
     }
     }
-    // 3. rare: footprints the box does not hold, through the gather kernel's sample().  uint16 frames here (their
-    //    border footprints take what the frame's box holds from LDS); float32 frames in a frame loop of their own
-    //    below, so that the coordinate source and the sampler's state are not live through THIS loop (round 6: 134 of
-    //    the bicubic kernel's 747 vector instructions per frame were v_readlane_b32 restores of spilled scalars)
-    if constexpr (kU16 || IPA_TILE_SLOW_INSIDE != 0) {
+    // 3. rare: footprints the box does not hold, through the gather kernel's sample() (uint16 frames: their border
+    //    footprints take what the frame's box holds from LDS).  (In a frame loop of their own behind this one the
+    //    float32 ones measured slower, round 6.)
     if (slow) {
 #pragma unroll 1
       for (int j = 0; j < kWarpTilePx; j++) {
@@ -814,26 +769,6 @@ tile_warp_kernel(TileWarpArgs a, Coord coord) {
                                                 (int)((long)y * a.dpitch + x) << kEsh, 0, 0);
         else
           store_px(tile_slow_sample<INTERP, C>(s, sx, sy, a.cval, kLzStride), y);
-      }
-    }
-    }
-  }
-  if constexpr (!kU16 && IPA_TILE_SLOW_INSIDE == 0) {
-    if (slow) {
-#pragma unroll 1
-      for (unsigned f = f0; f < f1; f++) {
-        s.rsrc = make_rsrc(a.src + (long)f * a.src_frame_bytes, a.src_bytes);
-        const __amdgpu_buffer_rsrc_t drs = make_rsrc(dst0 + (long)f * a.dst_frame_elems, a.dst_bytes);
-#pragma unroll 1
-        for (int j = 0; j < kWarpTilePx; j++) {
-          if (!((slow >> j) & 1u)) continue;
-          const int y = y0 + yl + kRowsPass * j;
-          if (x >= a.dw || y >= a.dh) continue;
-          C sx, sy;
-          coord.get(x, y, sx, sy);
-          const float o = tile_slow_sample<INTERP, C>(s, sx, sy, a.cval, kLzStride);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(o), drs, (int)((long)y * a.dpitch + x) << kEsh, 0, 0);
-        }
       }
     }
   }
@@ -940,8 +875,7 @@ static inline int tile_warp_pitch(const double* m, int dh, int dw, int min_pitch
   // bank is the column; round 6 counts every pitch: C5's bicubic warp under 7 degrees read its taps at 46 % conflict cycles)
   int best = min_pitch | 1;
   long best_cost = -1;
-  for (int P = IPA_TILE_PITCH_ODD ? (min_pitch | 1) : min_pitch; P < (min_pitch | 1) + (IPA_TILE_PITCH_ODD ? 32 : 33);
-       P += IPA_TILE_PITCH_ODD ? 2 : 1) {
+  for (int P = min_pitch; P < (min_pitch | 1) + 33; P++) {
     if (tile_warp_lds_bytes<NT>(P, rows) > kWarpTileLdsBytes) break;
     long cost = 0;
     for (int py = 0; py < 3; py++)

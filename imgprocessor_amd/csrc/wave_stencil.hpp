@@ -133,7 +133,7 @@ template <int K, bool HALO = false> struct wave_geom {
   static constexpr int NW = 4 + 2 * H;               // window a lane needs per row
 };
 #ifndef IPA_HALO
-#define IPA_HALO 1   // the hand-scheduled kernels (wave_pipe.hpp) use the aligned geometry
+#define IPA_HALO 1   // the hand-scheduled plain-row kernels use the aligned geometry (wave_pipe.hpp::geom_halo)
 #endif
 
 struct WaveParams {
@@ -438,10 +438,7 @@ template <typename ST, int INTERP, typename Coord> struct SampleRowSrc {
     static constexpr int value =
         INTERP == kLinear ? (K >= 9 ? IPA_SAMPLE_DEPTH_BIG : (kShared ? 1 : IPA_SAMPLE_DEPTH)) : 1;
   };
-  template <int D> struct Chunk {
-    BatchTaps<ST, INTERP, 4> t[D];
-    BatchTaps<ST, INTERP, 1> th[D];   // HALO geometry: the halo sample of lanes 0 .. 2H-1
-  };
+  template <int D> struct Chunk { BatchTaps<ST, INTERP, 4> t[D]; };
 
   Coord coord;
   const char* src;       // frame 0 of the remap source
@@ -558,35 +555,6 @@ template <typename ST, int INTERP, typename Coord> struct SampleRowSrc {
       }
 #pragma unroll
       for (int k = 0; k < 4; k++) row[64u * k + lane] = cur[k];
-    }
-  }
-  // HALO geometry, chunked loop (rim strips): the halo sample of lanes 0 .. 2H-1 through the
-  // same batch machinery (taps issued with the chunk's other loads, blended with its rows)
-  template <int D, int H, int QM = -1>
-  __device__ __forceinline__ void issue_halo(const Cols& c, const int (&vv)[D], Chunk<D>& ch) const {
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-      C hx[1], hy[1];
-      coord.get(c.uh < 0 ? 0 : c.uh, vv[d] < 0 ? 0 : vv[d], hx[0], hy[0]);
-      batch_issue<ST, INTERP, 1, QM>(s, hx, hy, ch.th[d]);
-    }
-  }
-  template <int D, int H>
-  __device__ __forceinline__ void stage_halo(const Cols& c, const int (&vv)[D], const Chunk<D>& ch,
-                                             float* xp) const {
-    const unsigned lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-      float cur = batch_blend_one<ST, INTERP, 1>(s, ch.th[d], 0);
-      if (!(ch.th[d].interior & 1u)) {
-        if (!batch_blend_border<ST, INTERP, 1>(s, ch.th[d], 0, cval, cur)) {
-          C hx, hy;
-          coord.get(c.uh < 0 ? 0 : c.uh, vv[d] < 0 ? 0 : vv[d], hx, hy);
-          cur = sample<ST, INTERP, C>(s, hx, hy, cval);
-        }
-      }
-      cur = (vv[d] < 0 || c.uh < 0) ? ccval : cur;
-      if (lane < 2u * H) xp[d * kRowStride + kRowPad - H + halo_pos<H>(lane)] = cur;
     }
   }
 };
@@ -873,10 +841,7 @@ __device__ __forceinline__ void wave_stencil_body(const WaveParams& p, Src src,
   // map rows shared by the frames of a workgroup (wave_run_strip_shared): a ring of 2 IPA_WPB rows
   constexpr bool kShared = (IPA_PIPE != 0) && (IPA_PIPE_SHARED != 0) && !STREAM &&
                            shared_capable<Src, K>::value;
-#ifndef IPA_DEBUG_LDS_PAD
-#define IPA_DEBUG_LDS_PAD 0   // measurement only: extra LDS floats per workgroup (lowers the occupancy)
-#endif
-  __shared__ __attribute__((aligned(16))) float mapring[(kShared ? 2 * IPA_WPB * ring_row<HALO>::value : 4) + IPA_DEBUG_LDS_PAD];
+  __shared__ __attribute__((aligned(16))) float mapring[kShared ? 2 * IPA_WPB * kRingRow : 4];
   if (sid >= p.strips) return;  // whole wave
   if (p.skip && p.skip[sid]) return;
   const int syi = (int)(sid / (unsigned)p.strips_x), sxi = (int)sid - syi * p.strips_x;
@@ -905,15 +870,15 @@ __device__ __forceinline__ void wave_stencil_body(const WaveParams& p, Src src,
       // the waves of this workgroup are frames of ONE strip: every wave takes this branch
       if (p.frames_wg) {
         DenseFilter<K> filt(wts);
-        if (src.q5) wave_run_strip_shared<K, 1, false, HALO>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
-        else wave_run_strip_shared<K, 0, false, HALO>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
+        if (src.q5) wave_run_strip_shared<K, 1, false>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
+        else wave_run_strip_shared<K, 0, false>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
         return;
       }
     }
     if constexpr (IPA_PIPE && !STREAM && pipe_unshared<Src, K>::value) {
       if constexpr (Src::kHasQ5) {
-        if (src.q5) wave_run_strip_pipe<K, 1, HALO>(p, src, wts, xp, c, y0, nrows, writer, dst);
-        else wave_run_strip_pipe<K, 0, HALO>(p, src, wts, xp, c, y0, nrows, writer, dst);
+        if (src.q5) wave_run_strip_pipe<K, 1>(p, src, wts, xp, c, y0, nrows, writer, dst);
+        else wave_run_strip_pipe<K, 0>(p, src, wts, xp, c, y0, nrows, writer, dst);
       } else {
         wave_run_strip_pipe<K, HALO, false>(p, src, wts, xp, c, y0, nrows, writer, dst);
       }
@@ -937,8 +902,8 @@ __device__ __forceinline__ void wave_stencil_body(const WaveParams& p, Src src,
       // rows resolved through the filter's border mode; 15 % of a 4K frame's strips)
       if (p.frames_wg && !p.no_pipe && src.vectors_ok() && p.vec_out && (p.dw & 3) == 0 && IPA_PIPE_EDGE) {
         DenseFilter<K> filt(wts);
-        if (src.q5) wave_run_strip_shared<K, 1, true, HALO>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
-        else wave_run_strip_shared<K, 0, true, HALO>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
+        if (src.q5) wave_run_strip_shared<K, 1, true>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
+        else wave_run_strip_shared<K, 0, true>(p, src, filt, xp, mapring, wave, c, y0, nrows, writer, dst);
         return;
       }
     }

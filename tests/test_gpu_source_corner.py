@@ -132,7 +132,7 @@ def test_every_lane_of_the_rim_strip(ia, oracle, loop, K):
     """the geometry the fuzzer found it on (143 x 1052 source, 4 frames, the corner in the leftmost strip), the
     corner moved through 16 columns so that its footprint visits every lane position of a quad and of the strip's
     reflected halo lanes: which lanes lost pixel (0, 0) depended on their neighbours' offsets (column 7: wrong,
-    column 1: right).  Round 5's rule (make VARIANT=r5corner DEFS=-DIPA_DEBUG_CORNER_AS_ROUND5 ONLY="fused_k3 fused_k5 ...")
+    column 1: right).  Round 5's rule (last buildable at commit cbe97cf)
     fails the default policy and the shared-footprint loop at 3x3 and 5x5, first with the corner in column 3."""
     from imgprocessor_amd import ops, _lib as L
     ctx = ia.default_context(0)

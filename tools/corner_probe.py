@@ -2,7 +2,7 @@
 """What makes the top-left-corner footprint of tools/fuzz_paths.py seed 63 case 66 come out wrong on the shared-footprint
 loop (round 6)?  Variations of that case, shared loop (frames_wg = 1) against the per-frame kernels (frames_wg = 0):
     IMGPROC_HIP_LIB=.../libimgproc_hip_r5corner.so python tools/corner_probe.py [dump.npz]
-(the r5corner build keeps round 5's rule: make VARIANT=r5corner DEFS=-DIPA_DEBUG_CORNER_AS_ROUND5 ONLY="fused_k3 ...")"""
+(the r5corner build keeps round 5's rule; it was last buildable at commit cbe97cf, whose wave_pipe.hpp has the switch)"""
 import os
 import sys
 
